@@ -20,13 +20,25 @@ The only collective of the path is ONE RCCL broadcast of the packed operator sta
 HBM; K steps enqueued on the library's HIP stream, bracketed by barrier + device synchronisation and by a HIP-event
 pair on that stream; MAX over ranks.  Rank 0 prints ONE JSON line.
 
+A plain run does only what `value` needs: set up, warm up, time the K steps (ONE repetition unless --repeats says
+otherwise), write the outputs when --dump-outputs DIR is given, print the line.  Everything else below (roofline and
+per-launch counters, A/B variants, projected scaling, measured peaks, cfg 2 / 4 / 5, the SURVEY section 8 rows, CPU
+baselines, the end-to-end solve; three repetitions of the K steps) runs with --full only; the --no-* options trim a
+--full run.  K + W may exceed the 1000 steps of the solve: the schedule is then run again from its start (same work
+per step), so --steps is always the number of steps timed.
+
+--dump-outputs DIR: after the timed steps, what the timed path computed in its last step, as float64 .npy files --
+final_state_sample.npy (a fixed, seeded sample of 1024 instances of rank 0's shard: (instances, n, 2) = real,
+imaginary part of the state), final_state_sample_instances.npy (their global indices) and final_state_norms.npy
+(the norm of every instance's state).  The inputs depend on the arguments only, so two builds can be compared.
+
 OUTPUT.  The LAST (and only) stdout line is a COMPACT object, below 6 KB (the driver keeps 8 018 characters of stdout):
-the contract fields, `roofline`, `cpu_baseline`, `cfg3_three_numbers` and one {value, unit, frac, bound} object per other
+the contract fields and, with --full, `roofline`, `cpu_baseline`, `cfg3_three_numbers` and one {value, unit, frac, bound} object per other
 configuration / SURVEY section 8 row (cfg2, cfg4, cfg5, sharded_cfg5, dense_expm, f2, f3, f4, projected_strong_scaling) --
 tools/bench_legs/compact.py.  The FULL result (every object described below, notes, A/B legs, term decompositions) goes to
 `bench_detail.json` beside this script (and to gpurun_out/ when that directory exists) and to stderr.
 
-Objects of the full result besides the contract fields:
+Objects of the full result of a --full run besides the contract fields:
   roofline                    dominant kernel of `value` (fp64-MFMA batched RHS contraction): `achieved` = EXECUTED
                               MFMA flops / launch time, `frac` = achieved / 78.6 TFLOP/s (a hardware fraction, <= 1);
                               the SURVEY 8(d) "useful" figure is kept as `useful_tflops`
@@ -314,6 +326,22 @@ def run_stub(args, D, json_out):
     D.close()
 
 
+DUMP_SAMPLE = 1024      # instances whose whole final state is written (16 MB at n = 1024); the norms cover every instance
+
+
+def dump_outputs(out_dir, final, first):
+    """--dump-outputs: the final states (B, n) complex128 of this rank's instances `first`..`first + B - 1` after the last
+    timed step, as float64 .npy files -- a fixed, seeded sample of the instances (the same for every run with the same
+    arguments), their global indices and the norm of every instance's state."""
+    os.makedirs(out_dir, exist_ok=True)
+    b = final.shape[0]
+    pick = np.sort(np.random.default_rng(1234).choice(b, size=min(b, DUMP_SAMPLE), replace=False))
+    sample = final[pick]
+    np.save(os.path.join(out_dir, "final_state_sample.npy"), np.stack([sample.real, sample.imag], axis=-1).astype(np.float64))
+    np.save(os.path.join(out_dir, "final_state_sample_instances.npy"), (first + pick).astype(np.float64))
+    np.save(os.path.join(out_dir, "final_state_norms.npy"), np.linalg.norm(final, axis=1).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -326,7 +354,13 @@ def main():
     ap.add_argument("--weak", action="store_true", help="weak scaling: --batch (4096) instances PER GPU")
     ap.add_argument("--torch-broadcast", action="store_true",
                     help="broadcast the stack with torch.distributed (RCCL) instead of the C-ABI midyn_stack_broadcast")
-    ap.add_argument("--repeats", type=int, default=3, help="timed repetitions of the K steps (spread is reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure (roofline, A/B variants, projected scaling, measured "
+                         "peaks, cfg 2 / 4 / 5, SURVEY-8 rows, CPU baselines, end-to-end solve); off: only the K timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the final states of the timed path (float64 .npy: a seeded sample + every norm) to DIR")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed repetitions of the K steps (spread is reported; default 3 with --full, else 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-single", action="store_true", help="skip the cfg-2 single-trajectory leg")
     ap.add_argument("--no-configs", action="store_true", help="skip the cfg-4 / cfg-5 legs")
@@ -419,19 +453,24 @@ def main():
     b_loc = hi - lo
     # schedule of the real 1000-step solve; the bench runs its first (warmup + repeats * steps) steps
     sched = FixedStepSchedule(cfg["t_span"], None, MAX_DT, _rk4_points)
-    repeats = max(1, args.repeats)
+    full = args.full
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    repeats = max(1, args.repeats if args.repeats is not None else (3 if full else 1))
     total = args.warmup + repeats * args.steps
     while total > len(sched.step_h) and repeats > 1:
         repeats -= 1
         total = args.warmup + repeats * args.steps
-    if total > len(sched.step_h):
-        raise SystemExit(f"warmup+steps must be <= {len(sched.step_h)}")
-    rows = sched.step_rows[:total]
+    if total <= len(sched.step_h):
+        rows, step_h = sched.step_rows[:total], sched.step_h[:total]
+    else:          # more steps than the solve has: its schedule again from the start (the same work in every step)
+        cyc = np.arange(total) % len(sched.step_h)
+        rows, step_h = sched.step_rows[cyc], sched.step_h[cyc]
     n_rows = int(rows.max()) + 1
     times = sched.times[:n_rows]
     table, amps, phs = sweep_table(workloads, times, lo, b_loc, k, cfg["carrier"], T_FINAL)
     y0 = cfg["y0"].reshape(-1, 1)
-    plan = qd.Rk4Plan(stack, times, table, rows, sched.step_h[:total], y0, b_loc, True)
+    plan = qd.Rk4Plan(stack, times, table, rows, step_h, y0, b_loc, True)
 
     def sync_all():
         ctx.synchronize()
@@ -454,6 +493,8 @@ def main():
     elapsed, event_ms = samples[0]        # the contract's "EXACTLY K steps": the first timed repetition
     final = plan.fetch()[:, :, 0]
     norm_dev = float(np.max(np.abs(np.linalg.norm(final, axis=1) - 1.0)))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, final, lo)
 
     evals = total_inst * 4 * args.steps
     value = evals / elapsed
@@ -464,7 +505,9 @@ def main():
     # launch duration from the SAME back-to-back region as ms_per_step: HIP events on the stream the kernel runs on
     # around the K steps, divided by the 4K launches (+ a per-launch event pass for the launch count / class check)
     prof_steps = min(args.steps, 10)
-    cnts = profile_pass(ctx, lambda: plan.run(total - prof_steps, total), ("rhs_gemm", "rhs_blocks_gemm", "rhs_combine"))
+    prof_classes = ("rhs_gemm", "rhs_blocks_gemm", "rhs_combine")
+    cnts = (profile_pass(ctx, lambda: plan.run(total - prof_steps, total), prof_classes) if full else
+            {c: {"launches": 0, "ms": 0.0} for c in prof_classes})        # a plain run: no roofline, no variants
     on_combine = cnts["rhs_combine"]["launches"] > 0        # sweeps: combine (MFMA over the operator planes) + apply (VALU)
     on_lists = cnts["rhs_blocks_gemm"]["launches"] > 0      # symmetry sectors: the contraction runs on tile work lists
     cnt = cnts["rhs_combine"] if on_combine else (cnts["rhs_blocks_gemm"] if on_lists else cnts["rhs_gemm"])
@@ -561,7 +604,7 @@ def main():
     def timed_variant(options, steps_=10):
         """ms per launch of the same sweep on a fresh plan created under `options` (routes are chosen at plan creation)."""
         with ctx.options(**options):         # (every option back to the value it had)
-            pv = qd.Rk4Plan(stack, times, table, rows, sched.step_h[:total], y0, b_loc, True)
+            pv = qd.Rk4Plan(stack, times, table, rows, step_h, y0, b_loc, True)
             w_steps = max(1, min(2, total - 1))
             d_steps = max(1, min(args.steps, steps_, total - w_steps))
             pv.run(0, w_steps)
@@ -644,7 +687,7 @@ def main():
     plan.close()
     # ---- what the N-GPU strong-scaling runs should show: the per-GPU shards of 2 / 4 / 8 ranks timed on THIS GPU --------
     projected = None
-    if rank == 0 and world == 1 and not args.dense and not args.weak and total_inst % 8 == 0 and not args.no_projection:
+    if full and rank == 0 and world == 1 and not args.dense and not args.weak and total_inst % 8 == 0 and not args.no_projection:
         projected = {"what": "strong scaling of this sweep projected from one GPU: the shard of an N-GPU run (instances / N) timed "
                              "here with the same plan type (best of three stretches of K steps); efficiency = shard rate / full rate, both "
                              "as the best of their repetitions.  The stack broadcast "
@@ -653,7 +696,7 @@ def main():
         for n_r in (2, 4, 8):
             b_s = total_inst // n_r
             tab_s = table[:b_s]
-            ps = qd.Rk4Plan(stack, times, tab_s, rows, sched.step_h[:total], y0, b_s, True)
+            ps = qd.Rk4Plan(stack, times, tab_s, rows, step_h, y0, b_s, True)
             # (warm-up over the first steps, then the best of up to three back-to-back stretches of the same length: a shard's
             # launches are short, and the first ones after a change of kernel shape run at unsettled clocks)
             w_steps = max(0, min(args.warmup, total - 1))
@@ -676,7 +719,7 @@ def main():
             projected["cfg3"][str(n_r)] = {"instances_per_gpu": b_s, "us_per_batched_evaluation": round(el_p / (4 * d_steps) * 1e6, 1),
                                           "projected_value": round(n_r * rate, 1), "efficiency": round(rate / max(rates), 4)}
     measured_peaks = None
-    if rank == 0 and world == 1:
+    if full and rank == 0 and world == 1:
         co = ctx.microbench("fp64_coissue", full=True)
         sus = ctx.microbench("mfma_f64_sustained", full=True)
         sus0 = ctx.microbench("mfma_f64_sustained_zero", full=True)
@@ -749,7 +792,7 @@ def main():
         out["measured_peaks"] = measured_peaks
 
     # ---- cfg 2: single trajectory, HBM-bound streaming kernel (rank 0, N=1) -------------------------------------
-    if rank == 0 and world == 1 and not args.no_single:
+    if full and rank == 0 and world == 1 and not args.no_single:
         s_total = min(len(sched.step_h), 1000)      # the whole configs[1] trajectory (one launch on the default route)
         rows1 = sched.step_rows[:s_total]
         nr1 = int(rows1.max()) + 1
@@ -843,7 +886,7 @@ def main():
     # ---- cfg 4 / cfg 5 (rank 0, N=1): the other BASELINE configurations with their rooflines --------------------
     cfg5 = None
     stack5 = None
-    want_cfg5 = not args.no_configs and not args.dense
+    want_cfg5 = full and not args.no_configs and not args.dense
     if rank == 0 and world == 1 and want_cfg5:
         try:
             out["cfg4"] = leg_cfg4(qd, ctx, workloads)
@@ -920,7 +963,7 @@ def main():
         stack5 = None
 
     # ---- CPU baseline: the NumPy oracle on this host, bounded sample (rank 0, N=1 only) -------------------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         ops, static, frame_im = host_arrays["v"][:3]
         out["cpu_baseline"] = leg_cpu_baseline(workloads, cfg, static, ops, frame_im, amps, phs)
         if not args.no_configs and not args.dense:
@@ -934,7 +977,7 @@ def main():
 
     # ---- the complete cfg-3 solve through the public Solver API: model build, signal evaluation, PCIe
     #      and result unpacking included (rank 0, N=1; --full-solve adds the host-table variant) ------------------
-    if rank == 0 and world == 1 and not args.no_end_to_end:
+    if full and rank == 0 and world == 1 and not args.no_end_to_end:
         t0f = time.perf_counter()
         solver = qd.Solver(static_hamiltonian=cfg["h_d"], hamiltonian_operators=cfg["ops"], rotating_frame=cfg["h_d"])
         t_model = time.perf_counter() - t0f

@@ -59,6 +59,14 @@ def _signals(qd, cfg, b, k=8):
             for a, nu, ph in zip(amps, cfg["carrier"], phases)]
 
 
+def _blas_threads(want):
+    """`want` BLAS threads, but never more than the BLAS pools were started with: the OpenBLAS builds bundled with NumPy
+    and SciPy crash (segmentation fault in zgemm) once threadpool_limits has grown a pool past its initial size."""
+    from threadpoolctl import threadpool_info
+
+    return max(1, min([want] + [p["num_threads"] for p in threadpool_info() if p.get("user_api") == "blas"]))
+
+
 def _oracle_final(cfg, model, b, t_span, y0):
     from oracle import dynamics_oracle as orc
     from qiskit_dynamics_amd import workloads
@@ -179,9 +187,9 @@ def test_expm_n4096_vs_scipy(qd, scale, kind):
         a = a - a.conj().T
     a *= scale / np.linalg.norm(a, 1)
     e = qd.default_context().expm(a)
-    with threadpool_limits(limits=32):
+    with threadpool_limits(limits=_blas_threads(32)):
         ref = scipy.linalg.expm(a)
     assert np.linalg.norm(e - ref, 1) / np.linalg.norm(ref, 1) < 1e-12
     if kind == "antiherm":
-        with threadpool_limits(limits=32):
+        with threadpool_limits(limits=_blas_threads(32)):
             assert np.linalg.norm(e.conj().T @ e - np.eye(n)) < 1e-12 * n

@@ -679,7 +679,7 @@ def test_bench_two_ranks_share_one_gpu():
     for k_ in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k_, None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--repeats", "1", "--no-configs"], env=env, capture_output=True, text=True, timeout=600)
+                        "--repeats", "1", "--full", "--no-configs"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout
@@ -706,7 +706,7 @@ def test_bench_line_of_a_real_run_fits_the_drivers_stdout_tail():
     env = dict(os.environ)
     for k_ in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k_, None)
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--repeats", "1",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--repeats", "1", "--full",
                         "--no-rows", "--no-variants", "--no-end-to-end", "--no-configs", "--no-projection"], env=env, capture_output=True,
                        text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -726,6 +726,44 @@ def test_bench_line_of_a_real_run_fits_the_drivers_stdout_tail():
     assert full["value"] == c["value"] and "note" in full["roofline"] and "roofline_single_trajectory" in full
 
 
+def test_bench_plain_run_times_only_the_steps_and_dumps_its_outputs(tmp_path):
+    """`python bench.py` without --full: the contract fields only (no roofline, CPU baseline or other configuration), exactly
+    --steps timed steps -- here with warm-up + steps beyond the 1000 steps of the solve, so the schedule runs again from its
+    start -- and --dump-outputs writes the final states of the timed path as float64 .npy files below 64 MB."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k_ in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k_, None)
+    dump = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "998",
+                        "--dump-outputs", str(dump)], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout
+    c = json.loads(lines[0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"} <= set(c)
+    assert not {"roofline", "cpu_baseline", "cfg2", "cfg4", "cfg5", "dense_expm", "end_to_end_solve"} & set(c)
+    assert c["steps"] == 4 and c["warmup"] == 998 and c["dtype"] == "f64" and c["higher_is_better"] is True
+    assert c["value"] == pytest.approx(4096 * 4 * 1e3 / c["ms_per_step"], rel=1e-3)
+    assert c["max_norm_deviation"] < 1e-8            # RK4 is not norm-preserving: ~5e-10 after these 1002 steps
+    files = sorted(os.listdir(dump))
+    assert files == ["final_state_norms.npy", "final_state_sample.npy", "final_state_sample_instances.npy"]
+    assert sum(os.path.getsize(dump / f) for f in files) < 64 * 2**20
+    sample = np.load(dump / "final_state_sample.npy")
+    idx = np.load(dump / "final_state_sample_instances.npy")
+    norms = np.load(dump / "final_state_norms.npy")
+    assert sample.dtype == idx.dtype == norms.dtype == np.float64
+    assert sample.shape == (1024, 1024, 2) and idx.shape == (1024,) and norms.shape == (4096,)
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 4096
+    assert np.max(np.abs(norms - 1.0)) == pytest.approx(c["max_norm_deviation"], rel=1e-3)
+    assert np.allclose(np.linalg.norm(sample[..., 0] + 1j * sample[..., 1], axis=1), norms[idx.astype(int)], rtol=0, atol=1e-14)
+
+
 def test_bench_two_ranks_share_one_gpu_with_the_sharded_cfg5_leg():
     """The same two self-spawned ranks WITH the second sharded leg of `bench.py --gpus N`: BASELINE configs[4] (n = 4096,
     Magnus-2, 1024 instances in total), 512 instances per rank -- every rank builds the 2.4 GB stack (one GPU: no RCCL
@@ -740,7 +778,8 @@ def test_bench_two_ranks_share_one_gpu_with_the_sharded_cfg5_leg():
     for k_ in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k_, None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--repeats", "1", "--no-projection", "--no-variants"], env=env, capture_output=True, text=True, timeout=900)
+                        "--repeats", "1", "--full", "--no-projection", "--no-variants"], env=env, capture_output=True, text=True,
+                       timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout

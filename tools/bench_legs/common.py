@@ -22,6 +22,17 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s achi
 # -----------------------------------------------------------------------------------------------------------------
 # helpers
 # -----------------------------------------------------------------------------------------------------------------
+def blas_threads(want):
+    """`want` BLAS threads, but never more than the BLAS pools were started with (OMP_NUM_THREADS / the CPU count at
+    import): the OpenBLAS builds bundled with NumPy and SciPy crash (segmentation fault in zgemm, e.g. inside
+    scipy.linalg.expm) once threadpool_limits has grown a pool past its initial size."""
+    import scipy.linalg  # noqa: F401  (SciPy's own BLAS pool is listed once it is loaded)
+    from threadpoolctl import threadpool_info
+
+    sizes = [p["num_threads"] for p in threadpool_info() if p.get("user_api") == "blas"]
+    return max(1, min([int(want)] + sizes))
+
+
 def measured_traffic(kernel_prefix):
     """(HBM bytes per dispatch, source) of the newest committed rocprofv3 PMC summary (profiles/*.traffic.json:
     FETCH_SIZE x2 per the gfx950 note + WRITE_SIZE, separate --pmc passes), or (None, None).  bench.py cannot collect

@@ -4,7 +4,7 @@ import time
 
 import numpy as np
 
-from .common import (ALL_CLASSES, CFG5_SWEEP, FP64_MFMA_PEAK_TFLOPS, HBM_PEAK_GBS, LDS_PEAK_GBS, MAX_DT, N_DRIVES, N_QUBITS, ROOT, SWEEP,  # noqa: F401
+from .common import (ALL_CLASSES, blas_threads, CFG5_SWEEP, FP64_MFMA_PEAK_TFLOPS, HBM_PEAK_GBS, LDS_PEAK_GBS, MAX_DT, N_DRIVES, N_QUBITS, ROOT, SWEEP,  # noqa: F401
                      T_FINAL, ZGEMM_NOTE, _mfma_roofline, build_diag_frame_stack, build_frame_basis_stack, build_model_stack,
                      measured_traffic, profile_pass, sweep_table)
 
@@ -16,7 +16,8 @@ def leg_cpu_baseline(workloads, cfg, static, ops, frame_im, amps, phs):
     a_d, a = static, ops
     d = 1j * frame_im
     best = None
-    for threads in sorted({8, 32, os.cpu_count() or 8}):      # short probe: which BLAS width is fastest here
+    widths = sorted({blas_threads(t) for t in (8, 32, os.cpu_count() or 8)})
+    for threads in widths:      # short probe: which BLAS width is fastest here
         if threads > (os.cpu_count() or 8):
             continue
         with threadpool_limits(limits=threads):
@@ -45,9 +46,9 @@ def leg_cpu_baseline(workloads, cfg, static, ops, frame_im, amps, phs):
     best = (n_inst * n_steps * 4 / cpu_s, threads, cpu_s)
     return {
         "value": round(best[0], 1), "unit": "RHS evals/s", "cores": best[1], "kind": "port",
-        "cores_for_blas3": min(os.cpu_count() or 8, 64),
+        "cores_for_blas3": blas_threads(min(os.cpu_count() or 8, 64)),
         "sample": f"{n_inst} instances x {n_steps} RK4 steps ({n_inst * n_steps * 4} RHS evals) of the same "
-                  f"model with the NumPy oracle (tensordot + matvec); best of BLAS thread counts 8/32/all on a "
+                  f"model with the NumPy oracle (tensordot + matvec); best of BLAS thread counts {'/'.join(map(str, widths))} (8/32/all, at most the pool size) on a "
                   f"{os.cpu_count()}-CPU host: {best[1]} threads, {best[2]:.1f} s",
         "host": {"cpu_count": os.cpu_count(), "numpy": np.__version__,
                  "blas": [f"{i.get('internal_api')} {i.get('version')} ({i.get('threading_layer') or i.get('user_api')})"

@@ -4,7 +4,7 @@ import time
 
 import numpy as np
 
-from .common import (ALL_CLASSES, CFG5_SWEEP, FP64_MFMA_PEAK_TFLOPS, HBM_PEAK_GBS, LDS_PEAK_GBS, MAX_DT, N_DRIVES, N_QUBITS, ROOT, SWEEP,  # noqa: F401
+from .common import (ALL_CLASSES, blas_threads, CFG5_SWEEP, FP64_MFMA_PEAK_TFLOPS, HBM_PEAK_GBS, LDS_PEAK_GBS, MAX_DT, N_DRIVES, N_QUBITS, ROOT, SWEEP,  # noqa: F401
                      T_FINAL, ZGEMM_NOTE, _mfma_roofline, build_diag_frame_stack, build_frame_basis_stack, build_model_stack,
                      measured_traffic, profile_pass, sweep_table)
 
@@ -36,7 +36,7 @@ def leg_dense_expm(qd, ctx):
             flops = ctx.executed_flops("zgemm")
         finally:
             ctx.set_option("profile", 0)
-        threads = min(os.cpu_count() or 8, 64)
+        threads = blas_threads(min(os.cpu_count() or 8, 64))
         with threadpool_limits(limits=threads):
             t0 = time.perf_counter()
             ref = scipy.linalg.expm(a)
@@ -101,7 +101,7 @@ def leg_lindblad_rk4(qd, ctx, workloads, n_qubits=10, instances=64, steps=5):
                                                                       cfg["h_d"])
     amps, phases = workloads.sweep_parameters(0, 8)
     rho_f = basis.conj().T @ cfg["rho0"] @ basis
-    threads = min(os.cpu_count() or 8, 64)
+    threads = blas_threads(min(os.cpu_count() or 8, 64))
     n_cpu = 4
     with threadpool_limits(limits=threads):
         t0 = time.perf_counter()
@@ -167,7 +167,7 @@ def leg_parallel_in_time(qd, ctx, workloads, n_qubits=4, steps=1000):
         ctx.set_option("profile", 0)
     # CPU: the reference's sequential loop (generator by tensordot, scipy.linalg.expm, matvec) on the superoperators, 20 steps
     s_d, s_ops = orc.vectorized_lindblad_stack(cfg["h_d"], cfg["ops"], cfg["static_dissipators"], None)
-    threads = 8
+    threads = blas_threads(8)
     n_cpu = 20
 
     def gen(t):

@@ -10,7 +10,7 @@ cd $R
 timeout 1500 python -m pytest tests -m gpu -q -x -p no:cacheprovider > $O/pytest.log 2>&1; echo "pytest exit $?" >> $O/pytest.log
 timeout 600 python tools/fuzz_routes.py --cases 200 --seed 0 > $O/fuzz_routes.log 2>&1
 timeout 600 python tools/fuzz_solver.py --cases 60 --seed 0 > $O/fuzz_solver.log 2>&1
-timeout 600 python bench.py --steps 5 --warmup 2 > $O/bench.json 2> $O/bench.err
+timeout 600 python bench.py --full --steps 5 --warmup 2 > $O/bench.json 2> $O/bench.err
 unset MIDYN_VARIANT_LOG
 python - <<'PY'
 import collections, os, re, subprocess, sys
