@@ -9,13 +9,13 @@ from ._lib import DynamicsError, HipLibraryError, Context, Stack, Rk4Plan, ExpmP
 from .signals import Signal, DiscreteSignal, SignalSum, DiscreteSignalSum, SignalList
 from .rotating_frame import RotatingFrame
 from .models import GeneratorModel, HamiltonianModel, LindbladModel
-from .solvers import Solver, solve_lmde, solve_ode
+from .solvers import Solver, solve_lmde, solve_ode, scipy_expm_solver
 from .perturbative import DysonSolver, MagnusSolver, ExpansionModel
 
 __all__ = [
     "DynamicsError", "HipLibraryError", "Context", "Stack", "Rk4Plan", "ExpmPlan", "default_context",
     "Signal", "DiscreteSignal", "SignalSum", "DiscreteSignalSum", "SignalList", "RotatingFrame",
-    "GeneratorModel", "HamiltonianModel", "LindbladModel", "Solver", "solve_lmde", "solve_ode",
+    "GeneratorModel", "HamiltonianModel", "LindbladModel", "Solver", "solve_lmde", "solve_ode", "scipy_expm_solver",
     "DysonSolver", "MagnusSolver", "ExpansionModel",
 ]
 __version__ = "0.1.0"

@@ -32,6 +32,10 @@ ABI_SYMBOLS = [
     "midyn_comm_get_unique_id", "midyn_comm_init_rank", "midyn_comm_destroy", "midyn_comm_count", "midyn_stack_create_empty",
     "midyn_stack_broadcast", "midyn_stack_broadcast_from",
 ]
+# every symbol include/midyn_gentable.h declares (LMDEs with a host-callable generator; tests/test_gentable_host.py)
+GENTABLE_SYMBOLS = [
+    "midyn_gentable_create", "midyn_gentable_push", "midyn_gentable_info", "midyn_gentable_finish", "midyn_gentable_destroy",
+]
 
 
 class DynamicsError(Exception):
@@ -188,7 +192,12 @@ def load():
         lib.midyn_stack_create_empty.argtypes = [_vp, _ci, _ci, _ci, _ci, P(_vp)]
         lib.midyn_stack_broadcast.argtypes = [_vp, _vp, _ci]
         lib.midyn_stack_broadcast_from.argtypes = [_vp, _vp, _vp, _ci]
-        for name in ABI_SYMBOLS:
+        lib.midyn_gentable_create.argtypes = [_vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _ci, _ci, _ci, _vp, P(_vp)]
+        lib.midyn_gentable_push.argtypes = [_vp, _ci, _ci, _vp]
+        lib.midyn_gentable_info.argtypes = [_vp, _vp]
+        lib.midyn_gentable_finish.argtypes = [_vp, _vp]
+        lib.midyn_gentable_destroy.argtypes = [_vp]
+        for name in ABI_SYMBOLS + GENTABLE_SYMBOLS:
             if name != "midyn_last_error":
                 getattr(lib, name).restype = _ci
         _lib = lib
@@ -681,6 +690,54 @@ class Stack:
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle and self.ctx.handle:
             self.ctx.lib.midyn_stack_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pylint: disable=broad-except
+            pass
+
+
+class GenTable:
+    """A fixed-step LMDE solve whose generator is sampled on the host (``midyn_gentable``, include/midyn_gentable.h).
+
+    ``step_rows`` / ``step_h`` / ``step_save`` / ``n_save`` as for ``Stack.expm_solve``; ``method`` 1..3 = Magnus order,
+    0 = RK4 step propagators (``parallel`` only); ``parallel`` = tree products between output times instead of the
+    propagators applied in step order.  Push the R sampled generators in order (``push``), then ``finish``."""
+
+    def __init__(self, ctx: "Context", n, y0, n_rows, step_rows, step_h, step_save, n_save, method, parallel):
+        self.ctx = ctx
+        self.handle = None
+        y0 = c128(y0)
+        self.n, self.m = int(n), int(y0.shape[1])
+        self.n_rows, self.n_save = int(n_rows), int(n_save)
+        step_rows, step_h, step_save = i32(step_rows).reshape(-1, 3), f64(step_h), i32(step_save)
+        h = _vp()
+        ctx.check(ctx.lib.midyn_gentable_create(
+            ctx.handle, self.n, self.m, self.n_rows, len(step_h), _ptr(step_rows), _ptr(step_h), _ptr(step_save),
+            self.n_save, int(method), int(bool(parallel)), _ptr(y0), ctypes.byref(h)))
+        self.handle = h
+        info = np.zeros(4, dtype=np.int64)
+        ctx.check(ctx.lib.midyn_gentable_info(self.handle, _ptr(info)))
+        self.steps_per_chunk, self.rows_per_push, self.n_pad, self.route = (int(v) for v in info)
+        self.pushed = 0
+
+    def push(self, rows):
+        """Rows ``[pushed, pushed + len(rows))``: a (k, n, n) complex128 block (copied before this returns)."""
+        rows = c128(rows)
+        self.ctx.check(self.ctx.lib.midyn_gentable_push(self.handle, self.pushed, int(rows.shape[0]), _ptr(rows)))
+        self.pushed += int(rows.shape[0])
+
+    def finish(self):
+        """(P, n, m) states at the save slots."""
+        out = np.empty((self.n_save, self.n, self.m), dtype=np.complex128)
+        self.ctx.check(self.ctx.lib.midyn_gentable_finish(self.handle, _ptr(out)))
+        return out
+
+    def close(self):
+        if getattr(self, "handle", None) is not None and self.handle and self.ctx.handle:
+            self.ctx.lib.midyn_gentable_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

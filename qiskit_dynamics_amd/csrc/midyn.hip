@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/midyn.h"
+#include "../../include/midyn_gentable.h"
 #include "midyn_kernels.h"
 #include "midyn_resident.h"
 #include "midyn_flip.h"
@@ -40,6 +41,7 @@ using namespace midyn;
 #include "midyn_sweep_plan.inc"
 #include "midyn_action.inc"
 #include "midyn_parallel.inc"
+#include "midyn_gentable.inc"
 #include "midyn_expansion.inc"
 #include "midyn_lindblad.inc"
 #include "midyn_microbench.inc"

@@ -4,11 +4,12 @@
 // -------------------------------------------------------------------------------------------------
 static thread_local std::string g_last_error;
 
-enum KClass { KC_STREAM = 0, KC_RHS_GEMM, KC_ZGEMM, KC_GEN, KC_ELEM, KC_BLOCKS, KC_BLOCKS_GEMM, KC_RESIDENT, KC_COMBINE, KC_COUNT };
+enum KClass { KC_STREAM = 0, KC_RHS_GEMM, KC_ZGEMM, KC_GEN, KC_ELEM, KC_BLOCKS, KC_BLOCKS_GEMM, KC_RESIDENT, KC_COMBINE, KC_GEN_CHAIN, KC_COUNT };
 static const char* kclass_names[KC_COUNT] = {"rhs_stream", "rhs_gemm", "zgemm", "gen_eval", "elementwise",
                                              "rhs_blocks", "rhs_blocks_gemm",   // block-sparse routes
                                              "rk4_resident",   // whole step ranges of one trajectory in one launch
-                                             "rhs_combine"};   // sweeps: combine (MFMA over the operator planes) + apply (midyn_combine.h)
+                                             "rhs_combine",   // sweeps: combine (MFMA over the operator planes) + apply (midyn_combine.h)
+                                             "gen_chain"};    // callable generators: a chunk of step propagators applied in one launch (midyn_gentable.inc)
 
 struct EventPair {
     hipEvent_t a, b;
@@ -43,6 +44,9 @@ struct midyn_ctx {
     int expansion_pack = 1;    // midyn_expansion_solve, n <= 32: two step matrices per padded 64 x 64 block (midyn_expansion.inc); 0: one
     int last_expansion_pack = 0;   // (steps per padded matrix of the last midyn_expansion_solve: counter "expansion_pack")
     int expm_plan_cache = 1;   // one-shot midyn_expm_solve on the sweep route keeps its plan in the stack (midyn_sweep_plan.inc); 0: made and destroyed per call
+    int gentable_chain = 1;    // midyn_gentable, sequential route, n_pad <= 128 and m <= 32: gen_chain_kernel (one launch per chunk); 0: a zgemm per step
+    int gentable_chunk = 0;    // midyn_gentable: > 0 caps the steps per chunk
+    double last_gentable[4] = {0, 0, 0, 0};   // last midyn_gentable solve: chunks, steps in the largest chunk, pinned staging bytes, device raw-row bytes
     int last_plan_cache = 0;   // (1: the last one-shot sweep solve found its plan in the stack; counter "expm_plan_cache")
     unsigned long long options_epoch = 1;      // counts midyn_ctx_set_option calls: cached plans are tied to the options they were made under
     int exchange_protocol = 0; // hand-offs between workgroups inside the one-launch kernels: 0 = the measured default (relaxed agent-scope
@@ -308,7 +312,8 @@ extern "C" int midyn_ctx_synchronize(midyn_ctx* ctx) {
     X(splitk_inlaunch)
 #define MIDYN_INT_OPTIONS(X)                                                                                             \
     X(ell_sweep_duo) X(ell_sweep_flip) X(sparse_bm) X(chebyshev) X(force_tile) X(ablate) X(stream_variant) X(ell_sweep_split) X(combine) X(combine_occupancy) X(combine_ablate) \
-    X(combine_sweep) X(expm_degree) X(krylov) X(force_splits) X(complex_3m) X(cheb_tail) X(expm_direct_out) X(exchange_protocol) X(expansion_pack) X(expm_plan_cache)
+    X(combine_sweep) X(expm_degree) X(krylov) X(force_splits) X(complex_3m) X(cheb_tail) X(expm_direct_out) X(exchange_protocol) X(expansion_pack) X(expm_plan_cache) \
+    X(gentable_chain) X(gentable_chunk)
 
 extern "C" int midyn_ctx_set_option(midyn_ctx* ctx, const char* name, long long value) {
     if (!ctx || !name) return fail(ctx, "midyn_ctx_set_option: NULL argument");
@@ -405,6 +410,16 @@ extern "C" int midyn_get_counters(midyn_ctx* ctx, const char* name, double* out)
     if (std::string(name) == "expm_plan_cache") {  // last one-shot sweep solve: (1 = plan found in the stack, 0 = made)
         out[0] = ctx->last_plan_cache;
         out[1] = 0.0;
+        return 0;
+    }
+    if (std::string(name) == "gentable_info") {   // last midyn_gentable solve: (chunks, steps in its largest chunk)
+        out[0] = ctx->last_gentable[0];
+        out[1] = ctx->last_gentable[1];
+        return 0;
+    }
+    if (std::string(name) == "gentable_staging") {   // ... (bytes of pinned host staging, bytes of device memory for raw rows)
+        out[0] = ctx->last_gentable[2];
+        out[1] = ctx->last_gentable[3];
         return 0;
     }
     if (std::string(name) == "expansion_pack") {  // last midyn_expansion_solve: (step matrices per padded 64 x 64 block: 1 or 2, 0)

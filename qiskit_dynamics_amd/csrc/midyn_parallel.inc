@@ -13,6 +13,93 @@
 // are formed here.  Products are re-associated, so results agree with the sequential methods to
 // rounding, not bit for bit (as in the reference, whose tests compare the two the same way).
 // -------------------------------------------------------------------------------------------------
+// Step 1 for a chunk of nb steps: the step propagators -> X[0..nb).  gen(gi, scale, out) writes scale * h_i G(t) at
+// the gi-th evaluation point of every step i of the chunk (the generators carry their step size, so Magnus serves steps
+// of different sizes with h = 1: Omega_m is homogeneous in h G).  Shared with midyn_gentable (midyn_gentable.inc).
+template <class Gen>
+static int form_step_propagators(midyn_ctx* ctx, int np, int nb, int method, Gen&& gen, DevBuf* G, DevBuf* W,
+                                 ExpmWork& w, double2* Xb) {
+    if (method == 0) {
+        double2 *k1 = G[0].as<double2>(), *gh = G[1].as<double2>(), *g1 = G[2].as<double2>();
+        double2 *k2 = W[0].as<double2>(), *k3 = W[1].as<double2>(), *k4 = W[2].as<double2>();
+        CHK(gen(0, 1.0, k1));
+        CHK(gen(1, 1.0, gh));
+        CHK(gen(2, 1.0, g1));
+        CHK(dev_sqgemm(ctx, nb, np, gh, k1, k2, 0.5, 1.0, gh));  // k2 = hG(t+h/2) (I + k1/2)
+        CHK(dev_sqgemm(ctx, nb, np, gh, k2, k3, 0.5, 1.0, gh));  // k3 = hG(t+h/2) (I + k2/2)
+        CHK(dev_sqgemm(ctx, nb, np, g1, k3, k4, 1.0, 1.0, g1));  // k4 = hG(t+h)   (I + k3)
+        const double2* xs[4] = {k1, k2, k3, k4};
+        double al[4] = {1.0 / 6, 1.0 / 3, 1.0 / 3, 1.0 / 6};
+        CHK(dev_lincomb(ctx, np, Xb, 4, xs, al, 1.0, nb));
+    } else {
+        CHK(magnus_omega(ctx, np, nb, method, 1.0, gen, G, W, Xb));  // generators carry h already
+        CHK(dev_expm_inplace(ctx, w, Xb, np, nullptr, nullptr, nb));
+    }
+    return 0;
+}
+
+// Steps 2 and 3 for a chunk: X holds 2 x cap matrices (the tree ping-pongs between the halves), step_save the save slots
+// of the chunk's steps; the state d_y[cur] ([np][ld]) advances through the chunk, the states at the output times go to
+// out[P][n][m].  Shared with midyn_gentable.
+static int tree_apply_chunk(midyn_ctx* ctx, int np, int ld, int nb, int cap, const int* step_save, double2* Xb,
+                            DevBuf& d_offs, DevBuf* d_y, int& cur, int n, int m, int P, double2* out,
+                            std::vector<int>& loc, std::vector<long long>& offs, std::vector<int>& round_start) {
+    const size_t mat = (size_t)np * np;
+    const size_t inst_elems = (size_t)n * m;
+    // -- 2. binary-tree products inside every interval [a, e) between output times
+    std::vector<std::pair<int, int>> segs;
+    for (int a = 0; a < nb;) {
+        int e = a;
+        while (e < nb && step_save[e] < 0) ++e;
+        e = std::min(nb, e + 1);
+        segs.emplace_back(a, e);
+        a = e;
+    }
+    std::fill(loc.begin(), loc.begin() + nb, 0);
+    auto slot = [&](int which, int i) { return (long long)((size_t)which * cap + i) * (long long)mat; };
+    int longest = 0;
+    for (auto& sg : segs) longest = std::max(longest, sg.second - sg.first);
+    // all levels' offset tables go to the device in ONE copy (a level has at most half the entries of
+    // the one before: fewer than nb products in total)
+    offs.clear();
+    round_start.clear();
+    for (int st = 1; st < longest; st *= 2) {
+        round_start.push_back((int)(offs.size() / 3));
+        for (auto& sg : segs)
+            for (int i = sg.first; i + st < sg.second; i += 2 * st) {
+                offs.push_back(slot(loc[i + st], i + st));  // later steps multiply from the left
+                offs.push_back(slot(loc[i], i));
+                offs.push_back(slot(loc[i] ^ 1, i));
+                loc[i] ^= 1;
+            }
+    }
+    round_start.push_back((int)(offs.size() / 3));
+    if (!offs.empty()) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the previous chunk may still read d_offs
+        HIPCHK(ctx, hipMemcpy(d_offs.p, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice));
+        for (size_t lv = 0; lv + 1 < round_start.size(); ++lv) {
+            const int cnt = round_start[lv + 1] - round_start[lv];
+            if (cnt > 0)
+                CHK(dev_zgemm_batched(ctx, cnt, np, np, np, Xb, np, 0, Xb, np, 0, Xb, np, 0, 1.0, 0.0, nullptr,
+                                      d_offs.as<long long>() + (size_t)3 * round_start[lv]));
+        }
+    }
+    // -- 3. apply the interval propagators in time order, store the states at the output times
+    for (auto& sg : segs) {
+        const double2* Q = Xb + slot(loc[sg.first], sg.first);
+        CHK(dev_zgemm(ctx, np, ld, np, Q, np, d_y[cur].as<double2>(), ld, d_y[cur ^ 1].as<double2>(), ld, 1.0,
+                      0.0, nullptr));
+        cur ^= 1;
+        const int sv = step_save[sg.second - 1];
+        if (sv >= 0) {
+            hipLaunchKernelGGL(gather_state_kernel, dim3(grid_for(inst_elems)), dim3(256), 0, ctx->stream,
+                               d_y[cur].as<double2>(), 1, n, m, ld, P, sv, out);
+            HIPCHK(ctx, hipGetLastError());
+        }
+    }
+    return 0;
+}
+
 extern "C" int midyn_parallel_solve(midyn_stack* s, int B, int m, int R, const double* times, const double* S,
                                     int nsteps, const int* step_rows, const double* step_h, const int* step_save,
                                     int P, int method, const midyn_complex* y0, int y0_shared,
@@ -99,73 +186,9 @@ extern "C" int midyn_parallel_solve(midyn_stack* s, int B, int m, int R, const d
                 return launch_gen_eval(s, k > 0 ? d_C[gi].as<double>() : nullptr,
                                        s->has_frame ? d_Eg[gi].as<double2>() : nullptr, scale, out, nb, k, np, hvec);
             };
-            if (method == 0) {
-                double2 *k1 = G[0].as<double2>(), *gh = G[1].as<double2>(), *g1 = G[2].as<double2>();
-                double2 *k2 = W[0].as<double2>(), *k3 = W[1].as<double2>(), *k4 = W[2].as<double2>();
-                CHK(gen(0, 1.0, k1));
-                CHK(gen(1, 1.0, gh));
-                CHK(gen(2, 1.0, g1));
-                CHK(dev_sqgemm(ctx, nb, np, gh, k1, k2, 0.5, 1.0, gh));  // k2 = hG(t+h/2) (I + k1/2)
-                CHK(dev_sqgemm(ctx, nb, np, gh, k2, k3, 0.5, 1.0, gh));  // k3 = hG(t+h/2) (I + k2/2)
-                CHK(dev_sqgemm(ctx, nb, np, g1, k3, k4, 1.0, 1.0, g1));  // k4 = hG(t+h)   (I + k3)
-                const double2* xs[4] = {k1, k2, k3, k4};
-                double al[4] = {1.0 / 6, 1.0 / 3, 1.0 / 3, 1.0 / 6};
-                CHK(dev_lincomb(ctx, np, Xb, 4, xs, al, 1.0, nb));
-            } else {
-                CHK(magnus_omega(ctx, np, nb, method, 1.0, gen, G, W, Xb));  // generators carry h already
-                CHK(dev_expm_inplace(ctx, w, Xb, np, nullptr, nullptr, nb));
-            }
-            // -- 2. binary-tree products inside every interval [a, e) between output times
-            std::vector<std::pair<int, int>> segs;
-            for (int a = 0; a < nb;) {
-                int e = a;
-                while (e < nb && step_save[c0 + e] < 0) ++e;
-                e = std::min(nb, e + 1);
-                segs.emplace_back(a, e);
-                a = e;
-            }
-            std::fill(loc.begin(), loc.begin() + nb, 0);
-            auto slot = [&](int which, int i) { return (long long)((size_t)which * cap + i) * (long long)mat; };
-            int longest = 0;
-            for (auto& sg : segs) longest = std::max(longest, sg.second - sg.first);
-            // all levels' offset tables go to the device in ONE copy (a level has at most half the entries of
-            // the one before: fewer than nb products in total)
-            offs.clear();
-            round_start.clear();
-            for (int st = 1; st < longest; st *= 2) {
-                round_start.push_back((int)(offs.size() / 3));
-                for (auto& sg : segs)
-                    for (int i = sg.first; i + st < sg.second; i += 2 * st) {
-                        offs.push_back(slot(loc[i + st], i + st));  // later steps multiply from the left
-                        offs.push_back(slot(loc[i], i));
-                        offs.push_back(slot(loc[i] ^ 1, i));
-                        loc[i] ^= 1;
-                    }
-            }
-            round_start.push_back((int)(offs.size() / 3));
-            if (!offs.empty()) {
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the previous chunk may still read d_offs
-                HIPCHK(ctx, hipMemcpy(d_offs.p, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice));
-                for (size_t lv = 0; lv + 1 < round_start.size(); ++lv) {
-                    const int cnt = round_start[lv + 1] - round_start[lv];
-                    if (cnt > 0)
-                        CHK(dev_zgemm_batched(ctx, cnt, np, np, np, Xb, np, 0, Xb, np, 0, Xb, np, 0, 1.0, 0.0, nullptr,
-                                              d_offs.as<long long>() + (size_t)3 * round_start[lv]));
-                }
-            }
-            // -- 3. apply the interval propagators in time order, store the states at the output times
-            for (auto& sg : segs) {
-                const double2* Q = Xb + slot(loc[sg.first], sg.first);
-                CHK(dev_zgemm(ctx, np, ld, np, Q, np, d_y[cur].as<double2>(), ld, d_y[cur ^ 1].as<double2>(), ld, 1.0,
-                              0.0, nullptr));
-                cur ^= 1;
-                const int sv = step_save[c0 + sg.second - 1];
-                if (sv >= 0) {
-                    hipLaunchKernelGGL(gather_state_kernel, dim3(grid_for(inst_elems)), dim3(256), 0, ctx->stream,
-                                       d_y[cur].as<double2>(), 1, s->n, m, ld, P, sv, d_out.as<double2>());
-                    HIPCHK(ctx, hipGetLastError());
-                }
-            }
+            CHK(form_step_propagators(ctx, np, nb, method, gen, G, W, w, Xb));
+            CHK(tree_apply_chunk(ctx, np, ld, nb, cap, step_save + c0, Xb, d_offs, d_y, cur, s->n, m, P, d_out.as<double2>(),
+                                 loc, offs, round_start));
         }
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         HIPCHK(ctx, hipMemcpy(Y_out + (size_t)b * P * inst_elems, d_out.p, (size_t)P * inst_elems * sizeof(double2),

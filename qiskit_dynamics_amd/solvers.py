@@ -7,6 +7,10 @@ list mode :556-590) restricted to the fixed-step methods of the hot path:
     method "RK4"  / "hip_RK4"        classic RK4          (fixed_step_solvers.py:43-77)
     method "scipy_expm" / "hip_expm" Magnus-1/2/3 + expm  (fixed_step_solvers.py:80-108,321-403)
 
+A generator given as a plain Python callable ``G(t)`` (``solve_lmde`` / ``scipy_expm_solver``) runs the LMDE methods
+only: the host samples ``G`` at the times of the fixed-step schedule and streams the samples to the device, which forms
+the step propagators and applies them (``_solve_callable``; include/midyn_gentable.h).
+
 Both spellings run the HIP kernels (there is no NumPy path in this package): user code written for
 the reference keeps its method strings.  The time loop of ``fixed_step_solver_template`` (:406-459)
 runs on the device; the host only (a) applies the step-count rule of ``get_fixed_step_sizes``
@@ -27,7 +31,7 @@ from typing import List, Optional, Tuple, Union
 import numpy as np
 from scipy.integrate._ivp.ivp import OdeResult
 
-from ._lib import DynamicsError, SignalTable
+from ._lib import DynamicsError, GenTable, SignalTable, default_context
 from .models import BaseGeneratorModel, GeneratorModel, HamiltonianModel, LindbladModel
 from .signals import Signal, SignalList, discrete_term_arrays
 
@@ -44,6 +48,8 @@ SOLVE_IVP_REAL_METHODS = ("LSODA", "Radau")
 SOLVE_IVP_METHODS = SOLVE_IVP_COMPLEX_METHODS + SOLVE_IVP_REAL_METHODS
 ODE_METHODS = list(RK4_METHODS + SOLVE_IVP_METHODS)
 LMDE_METHODS = list(EXPM_METHODS + RK4_PARALLEL_METHODS + EXPM_PARALLEL_METHODS)
+# the methods that take a generator given as a Python callable (every time they evaluate it at is known up front)
+CALLABLE_METHODS = EXPM_METHODS + EXPM_PARALLEL_METHODS + RK4_PARALLEL_METHODS
 
 
 # -------------------------------------------------------------------------------------------------
@@ -560,17 +566,92 @@ def _solve_ivp_device(model, t_span, y0, method, t_eval=None, signals=None, **kw
     return OdeResult(**fields)
 
 
+def validate_generator_sample(sample, t, n) -> np.ndarray:
+    """One sample ``G(t)`` of a callable generator as the (n, n) complex128 matrix the device reads; raises
+    ``DynamicsError`` naming ``t`` for a wrong shape or non-finite entries (checked before anything reaches the device)."""
+    g = np.asarray(sample)
+    if g.shape != (n, n):
+        raise DynamicsError(f"generator(t={float(t)!r}) returned an array of shape {g.shape}; the shape of y0 "
+                            f"requires ({n}, {n}).")
+    try:
+        g = g.astype(np.complex128, copy=False)
+    except (TypeError, ValueError) as exc:
+        raise DynamicsError(f"generator(t={float(t)!r}) is not a numeric array: {exc}") from None
+    if not np.isfinite(g).all():
+        raise DynamicsError(f"generator(t={float(t)!r}) has non-finite entries.")
+    return g
+
+
+def _solve_callable(generator, t_span, y0, method, t_eval=None, max_dt=None, magnus_order=1, **unknown) -> OdeResult:
+    """``solve_lmde`` with a callable generator (fixed_step_solvers.py:80-108 / :222-316): ``G`` is sampled on the host at
+    the schedule's times, one device chunk of rows at a time, and pushed to a ``GenTable`` that runs the chunks while the
+    next block is sampled.  No rotating frame and no basis change (the reference applies none either)."""
+    if unknown:
+        raise DynamicsError(f"Unsupported solver options for the HIP fixed-step methods: {sorted(unknown)}")
+    if max_dt is None:
+        raise DynamicsError("max_dt must be specified for fixed-step methods.")
+    y = np.asarray(y0, dtype=complex)
+    if y.ndim not in (1, 2):
+        raise DynamicsError(f"y0 must be 1-D (n,) or 2-D (n, m) for a callable generator, not of shape {y.shape}.")
+    vector = y.ndim == 1
+    y = np.ascontiguousarray(y.reshape(-1, 1) if vector else y)
+    n = y.shape[0]
+    if method in RK4_PARALLEL_METHODS:
+        sched = _cached_schedule(t_span, t_eval, max_dt, "rk4", _rk4_points)
+        code = 0
+    else:
+        sched = _cached_schedule(t_span, t_eval, max_dt, ("magnus", int(magnus_order)), _magnus_points(magnus_order))
+        code = int(magnus_order)
+    parallel = method not in EXPM_METHODS
+    ctx = default_context()
+    times = sched.times
+    t_wall = time.perf_counter()
+    table = GenTable(ctx, n, y, len(times), sched.step_rows, sched.step_h, sched.step_save, sched.n_save, code, parallel)
+    try:
+        block = max(1, table.rows_per_push)
+        for r0 in range(0, len(times), block):      # at most one block of samples on the host at a time
+            ts = times[r0:r0 + block]
+            rows = np.empty((len(ts), n, n), dtype=np.complex128)
+            for j, t in enumerate(ts):
+                rows[j] = validate_generator_sample(generator(t), t, n)
+            table.push(rows)
+        ys = table.finish()
+    finally:
+        table.close()
+    wall_s = time.perf_counter() - t_wall
+    t_out, y_out = sched.trim(ys)
+    if vector:
+        y_out = y_out[:, :, 0]
+    route = "generator_table+parallel_in_time" if parallel else "generator_table"
+    return OdeResult(t=t_out, y=np.ascontiguousarray(y_out), route=route, nfev=int(len(times)), wall_s=float(wall_s),
+                     device=f"hip:{ctx.device}")
+
+
 def solve_lmde(generator, t_span, y0, method: str = "RK4", t_eval=None, **kwargs) -> OdeResult:
-    """Solve ``y' = G(t) y`` for a model instance with a fixed-step HIP method."""
+    """Solve ``y' = G(t) y`` with a fixed-step HIP method, for a model instance or a callable ``G(t)``.
+
+    A callable generator takes the LMDE methods ``"scipy_expm"`` / ``"hip_expm"``, ``"hip_expm_parallel"`` /
+    ``"jax_expm_parallel"`` and ``"hip_RK4_parallel"`` / ``"jax_RK4_parallel"`` with ``max_dt`` and ``magnus_order``."""
     if not isinstance(generator, BaseGeneratorModel):
+        if callable(generator) and method in CALLABLE_METHODS:
+            return _solve_callable(generator, t_span, y0, method, t_eval=t_eval, **kwargs)
         raise DynamicsError(
-            "solve_lmde on the HIP path requires a model instance (GeneratorModel, HamiltonianModel "
-            "or LindbladModel); Python callables cannot be evaluated on the device.")
+            f"solve_lmde on the HIP path with method {method!r} requires a model instance (GeneratorModel, "
+            "HamiltonianModel or LindbladModel). A generator given as a Python callable is accepted by the LMDE methods "
+            f"{', '.join(repr(m_) for m_ in CALLABLE_METHODS)}; the ODE methods ('RK4', 'hip_RK4' and the solve_ivp "
+            "methods) would call it on the host at every stage.")
     if method in SOLVE_IVP_METHODS:   # ODE methods are accepted by solve_lmde (solver_functions.py:349-353)
         return _solve_ivp_device(generator, t_span, y0, method, t_eval=t_eval, **kwargs)
     if method not in RK4_METHODS + EXPM_METHODS + RK4_PARALLEL_METHODS + EXPM_PARALLEL_METHODS:
         raise DynamicsError(f"Method {method} not supported by solve_lmde.")
     return _solve_batch(generator, t_span, [y0], [None], method, t_eval=t_eval, **kwargs)[0]
+
+
+def scipy_expm_solver(generator, t_span, y0, max_dt, t_eval=None, magnus_order=1) -> OdeResult:
+    """The reference's ``scipy_expm_solver`` (solvers/fixed_step_solvers.py:80-108) for a callable ``G(t)``: Magnus
+    1/2/3 + expm on the device, the step propagators applied to ``y0`` in order (``solve_lmde(..., "scipy_expm")``)."""
+    return solve_lmde(generator, t_span, y0, method="scipy_expm", t_eval=t_eval, max_dt=max_dt,
+                      magnus_order=magnus_order)
 
 
 def solve_ode(rhs, t_span, y0, method: str = "RK4", t_eval=None, **kwargs) -> OdeResult:
