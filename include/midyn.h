@@ -89,6 +89,13 @@ const char* midyn_last_error(midyn_ctx* ctx);
  *                         formulation (the planes of a kind fill groups of four MFMA slots: at least three quarters of
  *                         the slots must hold a plane); 2: wherever the kernels apply; 0: the MFMA GEMM routes
  *   combine_min_cols [256]   ... smallest padded column count of the state block that takes it
+ *   combine_mirror [1]    ... on stacks whose time-dependent operators only couple the two row halves (L = the first n_pad / 2
+ *                         rows, U = the rest; no static operator in the frame) and whose planes satisfy
+ *                         A_p[U,L] = s_p A_p[L,U]^T to 16 eps max|A_p| (s_p = +1 imaginary, -1 real planes: -iH of a Hermitian H):
+ *                         each combined (L row group, U column block) entry is formed once and applied to both halves
+ *                         (csrc/midyn_combine_mirror.h; results equal the unmirrored kernel's to rounding).  1: RK4 stages /
+ *                         right-hand sides of sweeps with (n_pad / 64) (columns / 32) >= 8 x CUs (at least two waves per SIMD);
+ *                         2: wherever the stack is eligible; 0: never
  *   combine_occupancy [2]  waves per SIMD the workgroup shape of a SMALL sweep aims at: up to 8 waves split the list of one (row
  *                         group, instance block) pair and add their accumulators through LDS as a tree; 1: one wave per SIMD,
  *                         at most 4 waves per pair (the rule until round 4; A/B)
@@ -363,6 +370,9 @@ int midyn_expm_plan_destroy(midyn_expm_plan* plan);
  * per wave of that launch: 64, or 32 for stacks with more than two plane groups and for small sweeps, 0).  A one-launch RK4 sweep
  * (combine_sweep) counts as ONE "rhs_combine" launch; "combine_sweep" -> (workgroups of 16 instances, 10 x waves per
  * workgroup + 16-row tiles per wave) of the last one.
+ * "combine_mirror" -> (1 if the last "rhs_combine" launch was mirrored (combine_mirror_kernel: 8 or fewer pairs per workgroup,
+ * no split, 32 columns per wave; its U rows are finished by a "mirror_finish" launch) else 0, the stack's mirror defect in
+ * units of eps, or -1 where the stack is not eligible).
  * "flops:<class>" -> (real floating-point operations the dense MFMA contraction launches of that class executed while
  * `profile` was on -- per complex multiply-add 8 with four real products, 6 with three (3M), 4 for a one-plane operand --, 0):
  * what bench.py divides by the class's kernel time for the rooflines of the dense expm and the Lindblad products. */

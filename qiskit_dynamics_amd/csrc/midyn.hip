@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -27,6 +28,7 @@
 #include "midyn_resident.h"
 #include "midyn_flip.h"
 #include "midyn_combine.h"
+#include "midyn_combine_mirror.h"
 #include "midyn_combine_sweep.h"
 
 using namespace midyn;

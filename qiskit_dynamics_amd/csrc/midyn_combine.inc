@@ -10,6 +10,8 @@
 //   pack = true:  + the operator planes in MFMA operand order on the device; cmb_state 1
 // cmb_state -1: not applicable (no time-dependent operator, more than 8 planes of each kind / 16 of one kind alone
 // (combine_groups_ok), or a fragment array beyond 1 GiB or the device's free memory).
+static int stack_mirror_layout(midyn_stack* s);
+
 static int stack_combine_layout(midyn_stack* s, bool pack = true) {
     midyn_ctx* ctx = s->ctx;
     const int key = (ctx->skip_zero_planes ? 1 : 0) | (ctx->skip_zero_blocks ? 2 : 0);
@@ -134,11 +136,96 @@ static int stack_combine_layout(midyn_stack* s, bool pack = true) {
     hipLaunchKernelGGL(combine_pack_kernel, dim3((unsigned)entries), dim3(256), 0, ctx->stream, pa);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the host lists are released below)
+    CHK(stack_mirror_layout(s));
     std::vector<int>().swap(s->cmb_h_ptr);
     std::vector<int>().swap(s->cmb_h_idx);
     std::vector<int>().swap(s->cmb_h_rg);
     s->cmb_state = 1;
     pack_guard.done = true;
+    return 0;
+}
+
+// The mirrored form (midyn_combine_mirror.h), decided once per stack from the host lists of the pack step: eligible when no entry
+// of an L row group lies in L columns and none of a U row group in U columns (no static operator), and every plane of every
+// time-dependent segment satisfies max|A_p[U,L] - s_p A_p[L,U]^T| <= 16 eps max|A_p| (mirror_defect_kernel).  Sets of wpw L row
+// groups share a workgroup; their lists are merged into one walk (union of the kk blocks, the zero padding entry where a row
+// group has none).  No memory for the lists: not eligible (the unmirrored kernel takes every launch).
+static int stack_mirror_layout(midyn_stack* s) {
+    midyn_ctx* ctx = s->ctx;
+    s->mir_state = -1;
+    s->mir_defect = -1.0;
+    const int np = s->n_pad, half = np / 2, hb = half / 16, lgroups = half / CMB_ROWS;
+    if (s->cmb_stat != 0 || half % CMB_ROWS || lgroups < 1 || s->k < 1) return 0;
+    if (s->cmb_entries >= (1 << 19) || np / 16 > 4096) return 0;     // (entry << 12 | kk block in one int)
+    const std::vector<int>& ptr = s->cmb_h_ptr;
+    const std::vector<int>& idx = s->cmb_h_idx;
+    for (int rg = 0; rg < s->cmb_groups; ++rg)
+        for (int e = ptr[rg]; e < ptr[rg + 1]; ++e)
+            if ((rg < lgroups) != (idx[e] >= hb)) return 0;     // an entry in a diagonal quadrant
+    // the defect of the planes (one pass over the time-dependent segments)
+    const int nseg = s->nseg - s->has_static, nchunk = 64;
+    {
+        DevBuf d_part;
+        CHK(d_part.alloc(ctx, (size_t)nseg * nchunk * 4 * sizeof(double)));
+        hipLaunchKernelGGL(mirror_defect_kernel, dim3(nchunk, nseg), dim3(256), 0, ctx->stream, s->ops, np, s->has_static, nchunk,
+                           d_part.as<double>());
+        HIPCHK(ctx, hipGetLastError());
+        std::vector<double> part((size_t)nseg * nchunk * 4);
+        HIPCHK(ctx, hipMemcpyAsync(part.data(), d_part.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        double worst = 0.0;
+        for (int seg = 0; seg < nseg; ++seg)
+            for (int pl = 0; pl < 2; ++pl) {
+                double def = 0.0, mx = 0.0;
+                for (int c = 0; c < nchunk; ++c) {
+                    def = std::max(def, part[((size_t)seg * nchunk + c) * 4 + pl]);
+                    mx = std::max(mx, part[((size_t)seg * nchunk + c) * 4 + 2 + pl]);
+                }
+                if (def > 0.0) worst = std::max(worst, mx > 0.0 ? def / (DBL_EPSILON * mx) : INFINITY);
+            }
+        s->mir_defect = worst;
+        if (!(worst <= 16.0)) return 0;
+    }
+    int wpw = 8;
+    while (lgroups % wpw) wpw /= 2;
+    const int nsets = lgroups / wpw;
+    std::vector<int> sptr(nsets + 1, 0), skb, sent, cover((size_t)nsets * hb, 0);
+    for (int st = 0; st < nsets; ++st) {
+        std::vector<int> kbs;
+        for (int w = 0; w < wpw; ++w) {
+            const int rg = st * wpw + w;
+            kbs.insert(kbs.end(), idx.begin() + ptr[rg], idx.begin() + ptr[rg + 1]);
+        }
+        std::sort(kbs.begin(), kbs.end());
+        kbs.erase(std::unique(kbs.begin(), kbs.end()), kbs.end());
+        for (int kb : kbs) {
+            skb.push_back(kb);
+            cover[(size_t)st * hb + (kb - hb)] = 1;
+            for (int w = 0; w < wpw; ++w) {
+                const int rg = st * wpw + w;
+                const int* f = std::lower_bound(idx.data() + ptr[rg], idx.data() + ptr[rg + 1], kb);
+                const int e = f != idx.data() + ptr[rg + 1] && *f == kb ? (int)(f - idx.data()) : (int)s->cmb_entries;
+                sent.push_back(e << 12 | kb);
+            }
+        }
+        sptr[st + 1] = (int)skb.size();
+        if (sptr[st + 1] - sptr[st] > 64) return 0;     // (the kernel keeps a set's walk in the 64 lanes of a register)
+    }
+    const size_t words = sptr.size() + sent.size() + cover.size();
+    if (hipMalloc(&s->mir_ptr, words * sizeof(int)) != hipSuccess) {
+        s->mir_ptr = nullptr;
+        (void)hipGetLastError();
+        return 0;
+    }
+    s->mir_ent = s->mir_ptr + sptr.size();
+    s->mir_cover = s->mir_ent + sent.size();
+    HIPCHK(ctx, hipMemcpyAsync(s->mir_ptr, sptr.data(), sptr.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(s->mir_ent, sent.data(), sent.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(s->mir_cover, cover.data(), cover.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    s->mir_wpw = wpw;
+    s->mir_nsets = nsets;
+    s->mir_state = 1;
     return 0;
 }
 
@@ -167,6 +254,87 @@ static CombineFn combine_small_kernel_stat(int stat) {     // 32 instances per w
     }
 }
 
+using MirrorFn = void (*)(const MirrorArgs);
+using MirrorFinishFn = void (*)(const double2*, const int*, int, int, int, Epilogue);
+
+// The mirrored launch pair (combine_mirror_kernel + mirror_finish_kernel) when the stack, the options and the shape call for it;
+// *done = false: the caller runs the unmirrored kernel (no kernel for the plane layout, no memory for the partial sums).
+static int launch_combine_mirror(midyn_ctx* ctx, midyn_stack* s, const CombineArgs& a, int ld, bool* done) {
+    *done = false;
+    const int mode = a.epi.mode;
+    if (s->mir_state != 1 || ctx->combine_mirror == 0 || ctx->combine_ablate || ld % 32) return 0;
+    if (mode != EPI_RHS && mode != EPI_RK1 && mode != EPI_RK2 && mode != EPI_RK3 && mode != EPI_RK4) return 0;
+    // at least two waves per SIMD without splitting a list (n = 1024 on 256 CUs: from 4096 instances on)
+    if (ctx->combine_mirror == 1 && (long long)(s->n_pad / 64) * (ld / 32) < 2ll * 4 * ctx->num_cu) return 0;
+    MirrorFn fn = nullptr;
+    int slot = 0;
+#define MIDYN_CMM(R_, I_, SLOT_) \
+    if (s->cmb_nre4 == R_ && s->cmb_nim4 == I_) { fn = combine_mirror_kernel<R_, I_>; slot = SLOT_; }
+    MIDYN_CMM(0, 1, 0) MIDYN_CMM(0, 2, 1) MIDYN_CMM(1, 0, 2) MIDYN_CMM(2, 0, 3) MIDYN_CMM(1, 1, 4) MIDYN_CMM(2, 2, 5)
+#undef MIDYN_CMM
+    if (!fn) return 0;
+    MirrorFinishFn fin = mode == EPI_RHS ? mirror_finish_kernel<EPI_RHS> : mode == EPI_RK1 ? mirror_finish_kernel<EPI_RK1>
+                       : mode == EPI_RK2 ? mirror_finish_kernel<EPI_RK2> : mode == EPI_RK3 ? mirror_finish_kernel<EPI_RK3>
+                       : mirror_finish_kernel<EPI_RK4>;
+    const int half = s->n_pad / 2, wpw = s->mir_wpw, nsets = s->mir_nsets;
+    const size_t lds = (size_t)2 * wpw * 16 * 32 * sizeof(double2);
+    if (lds > ctx->lds_per_block) return 0;
+    const size_t part_bytes = (size_t)nsets * half * ld * sizeof(double2);
+    if (part_bytes > s->mir_part_bytes) {
+        if (s->mir_part) hipFree(s->mir_part);
+        s->mir_part = nullptr;
+        s->mir_part_bytes = 0;
+        if (hipMalloc(&s->mir_part, part_bytes) != hipSuccess) {
+            s->mir_part = nullptr;
+            (void)hipGetLastError();
+            return 0;
+        }
+        s->mir_part_bytes = part_bytes;
+    }
+    if (lds > 48 * 1024) {
+        static DeviceOnce attr[6];
+        if (attr[slot].needed(ctx->device)) {
+            HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            attr[slot].done(ctx->device);
+        }
+    }
+    MirrorArgs m{};
+    m.c = a;
+    m.c.stat = nullptr;
+    m.c.splits = 1;
+    m.c.wr = wpw;
+    m.set_ptr = s->mir_ptr;
+    m.set_ent = s->mir_ent;
+    m.wpw = wpw;
+    m.nsets = nsets;
+    m.half = half;
+    m.part = s->mir_part;
+    note_variant("combine_mirror_kernel", {s->cmb_nre4, s->cmb_nim4});
+    ctx->last_combine[0] = (double)s->cmb_entries;
+    ctx->last_combine[1] = s->cmb_nre4;
+    ctx->last_combine[2] = s->cmb_nim4;
+    ctx->last_combine[3] = s->cmb_stat;
+    ctx->last_combine[4] = wpw;
+    ctx->last_combine[5] = 1;
+    ctx->last_combine[6] = 32;
+    ctx->last_mirror[0] = 1;
+    ctx->last_mirror[1] = s->mir_defect;
+    {
+        ProfScope ps(ctx, KC_COMBINE);
+        hipLaunchKernelGGL(fn, dim3((unsigned)(nsets * (ld / 32))), dim3(64u * wpw), lds, ctx->stream, m);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    const size_t elems = (size_t)half * ld;
+    {
+        ProfScope ps(ctx, KC_MIRROR_FINISH);
+        hipLaunchKernelGGL(fin, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, ctx->stream,
+                           (const double2*)s->mir_part, (const int*)s->mir_cover, nsets, half, ld, a.epi);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    *done = true;
+    return 0;
+}
+
 // One evaluation  epilogue( sum_kk (G_d + sum_j c_j G_j)[r][kk] yin[kk][col] )  for all rows and the `ld` columns of yin.
 static int launch_combine(midyn_ctx* ctx, midyn_stack* s, const double2* yin, int ld, const double* coeff, long long inst_stride,
                           int m_cols, int n_inst, const Epilogue& epi) {
@@ -191,6 +359,13 @@ static int launch_combine(midyn_ctx* ctx, midyn_stack* s, const double2* yin, in
         a.epi.yin_next = nullptr;
         a.epi.e_cur = a.epi.e_next = nullptr;
     }
+    {
+        bool mirrored = false;
+        CHK(launch_combine_mirror(ctx, s, a, ld, &mirrored));
+        if (mirrored) return 0;
+    }
+    ctx->last_mirror[0] = 0;
+    ctx->last_mirror[1] = s->mir_defect;
     CombineFn fn = nullptr;
 #define MIDYN_CMB(R_, I_) \
     if (s->cmb_nre4 == R_ && s->cmb_nim4 == I_) fn = combine_kernel_stat<R_, I_>(s->cmb_stat);

@@ -4,12 +4,13 @@
 // -------------------------------------------------------------------------------------------------
 static thread_local std::string g_last_error;
 
-enum KClass { KC_STREAM = 0, KC_RHS_GEMM, KC_ZGEMM, KC_GEN, KC_ELEM, KC_BLOCKS, KC_BLOCKS_GEMM, KC_RESIDENT, KC_COMBINE, KC_GEN_CHAIN, KC_COUNT };
+enum KClass { KC_STREAM = 0, KC_RHS_GEMM, KC_ZGEMM, KC_GEN, KC_ELEM, KC_BLOCKS, KC_BLOCKS_GEMM, KC_RESIDENT, KC_COMBINE, KC_GEN_CHAIN, KC_MIRROR_FINISH, KC_COUNT };
 static const char* kclass_names[KC_COUNT] = {"rhs_stream", "rhs_gemm", "zgemm", "gen_eval", "elementwise",
                                              "rhs_blocks", "rhs_blocks_gemm",   // block-sparse routes
                                              "rk4_resident",   // whole step ranges of one trajectory in one launch
                                              "rhs_combine",   // sweeps: combine (MFMA over the operator planes) + apply (midyn_combine.h)
-                                             "gen_chain"};    // callable generators: a chunk of step propagators applied in one launch (midyn_gentable.inc)
+                                             "gen_chain",     // callable generators: a chunk of step propagators applied in one launch (midyn_gentable.inc)
+                                             "mirror_finish"};   // mirrored combine: sum of the U-row partials + their epilogue (midyn_combine_mirror.h)
 
 struct EventPair {
     hipEvent_t a, b;
@@ -69,6 +70,10 @@ struct midyn_ctx {
     int combine = 1;             // sweeps (many instances with their own coefficients): COMBINE + APPLY kernel instead of k + 1 GEMMs
                                  // (1: where it is the faster formulation, 2: wherever it applies, 0: never)
     int combine_min_cols = 256;  // ... from this many state columns on
+    int combine_mirror = 1;      // ... on stacks that only couple the two row halves, with symmetric / antisymmetric planes: each combined block
+                                 // formed once and applied twice (combine_mirror_kernel; 1: the RK4 / rhs route of sweeps with at least two
+                                 // mirror waves per SIMD, 2: wherever the stack is eligible, 0: never)
+    double last_mirror[2] = {0, 0};   // (1 if the last combine launch was mirrored, the stack's mirror defect in units of epsilon)
     int combine_ablate = 0;      // profiling only (results wrong): 1 = rhs_combine_kernel stores its result and nothing else (no fused RK4 /
                                  // series stage: none of the epilogue's reads, one of its two writes) -- what the epilogue of a launch costs
     int combine_occupancy = 2;   // waves per SIMD the workgroup shape of a small sweep aims at (list splits up to 8); 1: one wave, splits up to 4
@@ -311,7 +316,7 @@ extern "C" int midyn_ctx_synchronize(midyn_ctx* ctx) {
     X(ell_sweep_packed) X(multi_stream) X(expm_action) X(split_k) X(combine_first) X(plane_kernel) X(pair_launch)        \
     X(splitk_inlaunch)
 #define MIDYN_INT_OPTIONS(X)                                                                                             \
-    X(ell_sweep_duo) X(ell_sweep_flip) X(sparse_bm) X(chebyshev) X(force_tile) X(ablate) X(stream_variant) X(ell_sweep_split) X(combine) X(combine_occupancy) X(combine_ablate) \
+    X(ell_sweep_duo) X(ell_sweep_flip) X(sparse_bm) X(chebyshev) X(force_tile) X(ablate) X(stream_variant) X(ell_sweep_split) X(combine) X(combine_mirror) X(combine_occupancy) X(combine_ablate) \
     X(combine_sweep) X(expm_degree) X(krylov) X(force_splits) X(complex_3m) X(cheb_tail) X(expm_direct_out) X(exchange_protocol) X(expansion_pack) X(expm_plan_cache) \
     X(gentable_chain) X(gentable_chunk)
 
@@ -430,6 +435,11 @@ extern "C" int midyn_get_counters(midyn_ctx* ctx, const char* name, double* out)
     if (std::string(name) == "combine_shape") {  // ... ((row group, column block) pairs per workgroup, waves that split the list of one pair)
         out[0] = ctx->last_combine[4];
         out[1] = ctx->last_combine[5];
+        return 0;
+    }
+    if (std::string(name) == "combine_mirror") {   // ... (1 if it was mirrored (combine_mirror_kernel) else 0, the stack's mirror defect in units of eps)
+        out[0] = ctx->last_mirror[0];
+        out[1] = ctx->last_mirror[1];
         return 0;
     }
     if (std::string(name) == "combine_wave") {   // ... (state columns per wave: 64, or 32 -- wide stacks and small sweeps --, 0)
@@ -552,12 +562,28 @@ struct midyn_stack {
     int* cmb_ptr = nullptr;         // [cmb_groups + 1]
     int* cmb_idx = nullptr;         // kk block per entry
     int cmb_plane_col[24] = {0};    // coefficient column per plane slot (-1 padding)
+    // ... mirrored form (built with the fragments; midyn_combine_mirror.h)
+    int mir_state = 0;              // 1 eligible (lists below), -1 not
+    double mir_defect = 0.0;        // max_p max|A_p[U,L] - s_p A_p[L,U]^T| / (eps max|A_p|) (-1: not examined)
+    int mir_wpw = 0, mir_nsets = 0; // L row groups per workgroup, sets of them
+    int* mir_ptr = nullptr;         // [nsets + 1] | [union position][wpw] fragment entry << 12 | kk block | [set][U block] covered,
+    int* mir_ent = nullptr;         //   one allocation
+    int* mir_cover = nullptr;
+    double2* mir_part = nullptr;    // partial sums of the U rows [nsets][n_pad / 2][ld] (grown on demand)
+    size_t mir_part_bytes = 0;
 };
 
 static void stack_drop_combine(midyn_stack* s) {
     if (s->cmb_frags) hipFree(s->cmb_frags);
     if (s->cmb_ptr) hipFree(s->cmb_ptr);
     if (s->cmb_idx) hipFree(s->cmb_idx);
+    if (s->mir_ptr) hipFree(s->mir_ptr);
+    if (s->mir_part) hipFree(s->mir_part);
+    s->mir_ptr = s->mir_ent = s->mir_cover = nullptr;
+    s->mir_part = nullptr;
+    s->mir_part_bytes = 0;
+    s->mir_state = 0;
+    s->mir_defect = 0.0;
     s->cmb_frags = nullptr;
     s->cmb_ptr = s->cmb_idx = nullptr;
     s->cmb_state = 0;
