@@ -598,6 +598,13 @@ struct DevBuf {
         cap = want;
         return 0;
     }
+    // alloc + a synchronous copy of a host table (complete on return)
+    template <class T>
+    int upload(midyn_ctx* ctx, const std::vector<T>& v) {
+        CHK(alloc(ctx, v.size() * sizeof(T)));
+        HIPCHK(ctx, hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        return 0;
+    }
     template <class T>
     T* as() { return static_cast<T*>(p); }
 };

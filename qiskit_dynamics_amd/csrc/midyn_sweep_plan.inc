@@ -51,6 +51,16 @@ static int stack_seg_aux_norms(midyn_stack* s) {
     return 0;
 }
 
+// the per-segment norms step_bounds_kernel reads: [1-norm | infinity norm | 1-norm of the Hermitian part]
+static int stack_norm_table(midyn_stack* s, std::vector<double>* nrm) {
+    CHK(stack_seg_norms(s));
+    CHK(stack_seg_aux_norms(s));
+    *nrm = s->seg_norm1;
+    nrm->insert(nrm->end(), s->seg_norminf.begin(), s->seg_norminf.end());
+    nrm->insert(nrm->end(), s->seg_herm1.begin(), s->seg_herm1.end());
+    return 0;
+}
+
 // Bessel functions J_0..J_K of the first kind at x > 0 by Miller's backward recurrence (normalised with
 // J_0 + 2 sum J_2k = 1); K is chosen by the caller, the recurrence starts far enough above it.
 static std::vector<double> bessel_j(double x, int K) {
@@ -77,22 +87,31 @@ static std::vector<double> bessel_j(double x, int K) {
 // (cfg 4 without a frame, rho = 10.8: 36 instead of 160), no orthogonalisation, sweeps included.  rho comes from
 // the larger of the 1-norm and infinity-norm triangle bounds; the series is only used when the Hermitian part
 // is small enough that the polynomials cannot grow:  K sqrt(2 ||herm(Omega)|| / rho) <= 0.7.
-struct ChebPlan {
-    bool use = false;
+//
+// The series of one step, the one policy of every expm action route and of the sweep plan: the scaled Taylor series (deg, sc)
+// is always set -- a caller that cannot run the Chebyshev series falls back to it -- and `cheb` says that the Chebyshev series
+// (K, reps, rho, coef) runs instead.
+struct StepSeries {
+    int deg = 2, sc = 1;        // Taylor: degree, repetitions (action_choose)
+    bool cheb = false;
     int reps = 1, K = 0;
     double rho = 0.0;           // bound of the whole Omega; every repetition applies expm(Omega / reps)
     std::vector<double> coef;   // J_k(rho / reps), k = 0..K
 };
-// rho_bound / herm: the step's bounds of Omega and of its Hermitian part (step_bounds_kernel).
+// taylor_bound >= ||Omega||_1 chooses the Taylor series; rho_bound / herm: the step's bounds of Omega and of its Hermitian part
+// (step_bounds_kernel); the Chebyshev series (only when allow_cheb) is for rho = max(cheb_at_least, rho_bound).
 // equal_cost: the caller's kernel runs a Chebyshev term for the price of a Taylor term (the one-launch sweep kernels: the
 // recurrence's second addend is a register) -- the series is taken as soon as it has fewer terms; elsewhere the Chebyshev
 // epilogue reads one more vector per term and the series must be a fifth shorter
-static void cheb_series(const midyn_ctx* ctx, int magnus_order, double rho_bound, double herm, double at_least, long long taylor_products,
-                        bool equal_cost, ChebPlan* out) {
-    *out = ChebPlan();
-    if (!ctx->chebyshev || magnus_order > 2) return;
-    const double rho = std::max(at_least, rho_bound);
-    if (!(rho > 0.0) || !std::isfinite(rho)) return;
+static int step_series(midyn_ctx* ctx, int magnus_order, double taylor_bound, double rho_bound, double herm, double cheb_at_least,
+                       bool allow_cheb, bool equal_cost, StepSeries* out) {
+    *out = StepSeries();
+    if (!std::isfinite(taylor_bound)) return fail(ctx, "midyn_expm_solve: non-finite generator norm");
+    action_choose(taylor_bound, &out->deg, &out->sc);
+    const long long taylor_products = (long long)out->deg * out->sc;
+    if (!allow_cheb || !ctx->chebyshev || magnus_order > 2) return 0;
+    const double rho = std::max(cheb_at_least, rho_bound);
+    if (!(rho > 0.0) || !std::isfinite(rho)) return 0;
     const int reps = std::max(1, (int)std::ceil(rho / 128.0));  // Bessel table accurate to a few 1e-15 up to here
     const double arg = rho / reps;
     const int kmax = (int)(arg + 10.0 * std::cbrt(arg) + 40.0);
@@ -109,17 +128,18 @@ static void cheb_series(const midyn_ctx* ctx, int magnus_order, double rho_bound
     } else {
         while (K > 1 && std::fabs(coef[K]) < 1e-18) --K;
     }
-    if (K >= kmax) return;
+    if (K >= kmax) return 0;
     const bool stable = (double)K * std::sqrt(2.0 * herm / rho) <= 0.7;
     const bool shorter = equal_cost && ctx->cheb_tail ? (long long)reps * K < taylor_products
                                                       : (long long)reps * (K + 1) * 10 < taylor_products * 8;
-    if (!stable || !(shorter || ctx->chebyshev >= 2)) return;
+    if (!stable || !(shorter || ctx->chebyshev >= 2)) return 0;
     coef.resize(K + 1);
-    out->use = true;
+    out->cheb = true;
     out->reps = reps;
     out->K = K;
     out->rho = rho;
     out->coef = std::move(coef);
+    return 0;
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -250,8 +270,8 @@ static int expm_plan_create_impl(midyn_stack* s, int B, int m, int R, const doub
     p->y0.assign(y0, y0 + y0_elems);
     CHK(expm_plan_sweep_route(s, B, m, magnus_order, nsteps, &p->sweep));
     if (p->sweep) {
-        CHK(stack_seg_norms(s));
-        CHK(stack_seg_aux_norms(s));
+        std::vector<double> nrm;
+        CHK(stack_norm_table(s, &nrm));
         const int np = s->n_pad;
         if (s->k > 0) CHK(p->d_S.alloc(ctx, (size_t)B * R * s->k * sizeof(double)));
         CHK(p->d_y0.alloc(ctx, y0_elems * sizeof(double2)));
@@ -269,13 +289,6 @@ static int expm_plan_create_impl(midyn_stack* s, int B, int m, int R, const doub
         p->dev_rows = reinterpret_cast<const int*>(p->d_static.as<double>() + nsteps);
         p->dev_save = step_save ? p->dev_rows + 3 * (size_t)nsteps : nullptr;
         HIPCHK(ctx, hipMemcpyAsync(p->d_y0.p, y0, y0_elems * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
-        // per-segment norms for the bounds kernel: [1-norm | infinity norm | 1-norm of the Hermitian part]
-        std::vector<double> nrm((size_t)3 * s->nseg);
-        for (int seg = 0; seg < s->nseg; ++seg) {
-            nrm[seg] = s->seg_norm1[seg];
-            nrm[s->nseg + seg] = s->seg_norminf[seg];
-            nrm[2 * s->nseg + seg] = s->seg_herm1[seg];
-        }
         CHK(p->d_nrm.alloc(ctx, nrm.size() * sizeof(double)));
         HIPCHK(ctx, hipMemcpyAsync(p->d_nrm.p, nrm.data(), nrm.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         CHK(p->d_bounds.alloc(ctx, (size_t)3 * nsteps * sizeof(double)));
@@ -675,16 +688,22 @@ static bool expm_plan_block(midyn_expm_plan* p, const void* ptr, size_t bytes, v
     return true;
 }
 
+// MIDYN_TIMING=1: wall-clock marks of a call on stderr, from its entry (where a solve's host time goes; diagnostics only)
+struct TimingMarks {
+    const char* fn;
+    std::chrono::steady_clock::time_point t_entry = std::chrono::steady_clock::now();
+    void operator()(const char* what) const {
+        static const bool timing = std::getenv("MIDYN_TIMING") != nullptr;
+        if (timing)
+            std::fprintf(stderr, "[midyn timing] %s %-28s %8.1f us\n", fn, what,
+                         std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_entry).count());
+    }
+};
+
 static int expm_plan_run_impl(midyn_expm_plan* p, const double* S, midyn_complex* Y_direct) {
     midyn_stack* s = p->stack;
     midyn_ctx* ctx = s->ctx;
-    static const bool timing = std::getenv("MIDYN_TIMING") != nullptr;
-    const auto t_entry = std::chrono::steady_clock::now();
-    auto mark = [&](const char* what) {
-        if (timing)
-            std::fprintf(stderr, "[midyn timing] expm_plan_run %-28s %8.1f us\n", what,
-                         std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_entry).count());
-    };
+    const TimingMarks mark{"expm_plan_run"};
     if (s->k > 0 && !S) return fail(ctx, "midyn_expm_plan_run: NULL coefficient table");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int B = p->B, nsteps = p->nsteps, magnus_order = p->order;
@@ -729,26 +748,19 @@ static int expm_plan_run_impl(midyn_expm_plan* p, const double* S, midyn_complex
     p->Kv.assign(nsteps, 0);
     p->repv.assign(nsteps, 1);
     p->parv.assign(nsteps, 1.0);
+    StepSeries ser;
     for (int st = 0; st < nsteps; ++st) {
-        const double bound = h_bounds[3 * st], rho_b = h_bounds[3 * st + 1], herm = h_bounds[3 * st + 2];
-        if (!std::isfinite(bound)) return fail(ctx, "midyn_expm_solve: non-finite generator norm");
-        int deg = 2, sc = 1;
-        action_choose(bound, &deg, &sc);
+        const double* const nb = h_bounds + 3 * st;     // 1-norm bound, rho, Hermitian part
         // (cfg 5, rho ~ 0.1 per step: 7-8 Chebyshev terms against Taylor degree 9 -- 150 instead of 180 terms per instance)
-        ChebPlan cp;
-        cheb_series(ctx, magnus_order, rho_b, herm, bound, (long long)deg * sc, true, &cp);
+        CHK(step_series(ctx, magnus_order, nb[0], nb[1], nb[2], nb[0], true, true, &ser));
         double* const row = h_coef + (size_t)st * EXPM_PLAN_STRIDE;
         std::fill(row, row + EXPM_PLAN_STRIDE, 0.0);
-        if (cp.use && cp.K + 1 <= EXPM_PLAN_STRIDE) {
-            p->Kv[st] = cp.K;
-            p->repv[st] = cp.reps;
-            p->parv[st] = cp.rho;
-            std::copy(cp.coef.begin(), cp.coef.end(), row);
-        } else {
-            p->Kv[st] = -deg;
-            p->repv[st] = sc;
-            p->parv[st] = (double)sc;
-        }
+        // a negative K = Taylor of degree -K; par = rho (Chebyshev) or sc (Taylor)
+        const bool cheb = ser.cheb && ser.K + 1 <= EXPM_PLAN_STRIDE;
+        p->Kv[st] = cheb ? ser.K : -ser.deg;
+        p->repv[st] = cheb ? ser.reps : ser.sc;
+        p->parv[st] = cheb ? ser.rho : (double)ser.sc;
+        if (cheb) std::copy(ser.coef.begin(), ser.coef.end(), row);
         h_K[st] = p->Kv[st];
         h_rep[st] = p->repv[st];
         h_par[st] = p->parv[st];

@@ -290,7 +290,7 @@ def test_results_in_pinned_arrays_survive_later_solves(qd):
 
 @pytest.mark.parametrize("n,magn", [(200, 9.0), (128, 2.0)])
 def test_chebyshev_series_ends_at_the_unit_roundoff(qd, n, magn):
-    """Option cheb_tail (csrc/midyn_action.inc, cheb_plan): the Chebyshev series of the expm action ends where the dropped terms
+    """Option cheb_tail (csrc/midyn_sweep_plan.inc, step_series): the Chebyshev series of the expm action ends where the dropped terms
     of a step sum to less than 2^-53 (default) instead of keeping every Bessel coefficient >= 1e-18 (cheb_tail = 0, rounds 2-5).
     The default must take FEWER products, agree with the old rule to a few ulps per step, and both must agree with the dense
     expm route and with the oracle's scipy.linalg.expm steps (solvers/fixed_step_solvers.py:80-108) at the solve tolerance."""
@@ -390,3 +390,44 @@ def test_exchange_protocol_option_is_bit_identical(qd):
     assert abs(np.linalg.norm(got[0][0]) - 1.0) < 1e-10 and np.max(np.abs(np.linalg.norm(got[0][3][:, -1, :, 0], axis=1) - 1.0)) < 1e-12
     assert ctx.counters("resident_fallbacks")["launches"] == gave_up
     assert ctx.get_option("exchange_protocol") == 0
+
+
+@pytest.mark.parametrize("route", ["sweep_plan", "per_launch", "dense"])
+def test_expm_solve_refuses_a_save_slot_beyond_the_result_before_any_launch(qd, route):
+    """midyn_expm_solve checks every save slot against the P slots per instance of the result block at its entry: a slot >= P
+    fails with "save slot" on every route -- the one-launch sweep plan, the per-launch expm action and the dense expm -- and
+    before any kernel has run.  The same solve with the valid slots runs on that route."""
+    from qiskit_dynamics_amd import workloads as W
+    from qiskit_dynamics_amd.rotating_frame import RotatingFrame
+    from qiskit_dynamics_amd.solvers import FixedStepSchedule, _magnus_points
+
+    ctx = qd.default_context()
+    cfg = W.schrodinger_config(n_qubits=10, n_drives=8, t_final=1.0, max_dt=0.25)
+    fr = RotatingFrame(np.diag(cfg["h_d"]).real.copy())
+    stack = qd.Stack(ctx, -1j * cfg["ops"], -1j * cfg["h_d"] - np.diag(fr.frame_diag), fr.frame_diag_imag)
+    sched = FixedStepSchedule(cfg["t_span"], None, cfg["max_dt"], _magnus_points(2))
+    count = 4
+    amps = np.array([W.sweep_parameters(i, 8)[0] for i in range(count)])
+    phases = np.array([W.sweep_parameters(i, 8)[1] for i in range(count)])
+    table = W.gaussian_coefficient_table(sched.times, amps, phases, cfg["carrier"], 1.0)
+    y0 = cfg["y0"].reshape(-1, 1)
+    bad = np.array(sched.step_save, dtype=np.int32)
+    bad[-1] = sched.n_save
+    opts = {"sweep_plan": {}, "per_launch": {"ell_sweep": 0}, "dense": {"expm_action": 0}}[route]
+    kernels = ("rk4_resident", "rhs_stream", "rhs_gemm", "rhs_blocks", "rhs_blocks_gemm", "rhs_combine", "zgemm", "gen_eval",
+               "elementwise")
+    with ctx.options(profile=1, **opts):
+        ctx.reset_counters()
+        stack.expm_solve(sched.times, table, sched.step_rows, sched.step_h, sched.step_save, sched.n_save, 2, y0, count, True)
+        ran = {c: ctx.counters(c)["launches"] for c in kernels}
+        ctx.reset_counters()
+        with pytest.raises(qd.DynamicsError, match="save slot"):
+            stack.expm_solve(sched.times, table, sched.step_rows, sched.step_h, bad, sched.n_save, 2, y0, count, True)
+        refused = {c: ctx.counters(c)["launches"] for c in kernels}
+    if route == "sweep_plan":
+        assert ran["rk4_resident"] >= 1, ran
+    elif route == "per_launch":
+        assert ran["rk4_resident"] == 0 and ran["zgemm"] == 0 and sum(ran.values()) > 0, ran
+    else:
+        assert ran["zgemm"] > 0, ran
+    assert not any(refused.values()), refused
