@@ -137,7 +137,12 @@ const char* midyn_last_error(midyn_ctx* ctx);
  *   expm_action [1]       few columns, Magnus order <= 2: expm(Omega) y by matrix-vector products
  *   expm_degree [0]       0: Taylor degree of the dense expm chosen from the norm; else 2|4|6|9|12|16
  *   profile [0]           record HIP-event kernel times (midyn_get_counters)
- *   stream_variant, plane_kernel, prefer_duo, ablate          A/B and profiling switches */
+ *   stream_variant, plane_kernel, prefer_duo, ablate          A/B and profiling switches
+ *   combine_ablate [0]    profiling only, results wrong: 1 = rhs_combine_kernel stores its result and nothing else (no fused
+ *                         RK4 / series epilogue); the mirrored route is not taken while it is set
+ *   mirror_ablate [0]     profiling only, results wrong: mirror_probe_kernel<N> in place of combine_mirror_kernel<0, 2>.
+ *                         1 = no global loads in the kk loop (every step re-uses the first step's fragments), 2 = no phase
+ *                         behind the block barrier (no cross-wave sum, no store of the partial sums), 3 = both */
 int midyn_ctx_set_option(midyn_ctx* ctx, const char* name, long long value);
 /* The present value of an option: what a caller that changes one for a while puts back afterwards (unknown name: error). */
 int midyn_ctx_get_option(midyn_ctx* ctx, const char* name, long long* value);

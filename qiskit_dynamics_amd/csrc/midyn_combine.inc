@@ -272,12 +272,17 @@ static int launch_combine_mirror(midyn_ctx* ctx, midyn_stack* s, const CombineAr
     if (s->cmb_nre4 == R_ && s->cmb_nim4 == I_) { fn = combine_mirror_kernel<R_, I_>; slot = SLOT_; }
     MIDYN_CMM(0, 1, 0) MIDYN_CMM(0, 2, 1) MIDYN_CMM(1, 0, 2) MIDYN_CMM(2, 0, 3) MIDYN_CMM(1, 1, 4) MIDYN_CMM(2, 2, 5)
 #undef MIDYN_CMM
+    if (ctx->mirror_ablate >= 1 && ctx->mirror_ablate <= 3 && slot == 1) {   // profiling only (results wrong)
+        fn = ctx->mirror_ablate == 1 ? mirror_probe_kernel<1> : ctx->mirror_ablate == 2 ? mirror_probe_kernel<2> : mirror_probe_kernel<3>;
+        slot = 5 + ctx->mirror_ablate;
+    }
     if (!fn) return 0;
     MirrorFinishFn fin = mode == EPI_RHS ? mirror_finish_kernel<EPI_RHS> : mode == EPI_RK1 ? mirror_finish_kernel<EPI_RK1>
                        : mode == EPI_RK2 ? mirror_finish_kernel<EPI_RK2> : mode == EPI_RK3 ? mirror_finish_kernel<EPI_RK3>
                        : mirror_finish_kernel<EPI_RK4>;
     const int half = s->n_pad / 2, wpw = s->mir_wpw, nsets = s->mir_nsets;
-    const size_t lds = (size_t)2 * wpw * 16 * 32 * sizeof(double2);
+    // partial sums 2 x wpw x 8 KB + stage input 2 x 8 KB (144 KB with eight waves)
+    const size_t lds = ((size_t)2 * wpw + 2) * 16 * 32 * sizeof(double2);
     if (lds > ctx->lds_per_block) return 0;
     const size_t part_bytes = (size_t)nsets * half * ld * sizeof(double2);
     if (part_bytes > s->mir_part_bytes) {
@@ -290,11 +295,17 @@ static int launch_combine_mirror(midyn_ctx* ctx, midyn_stack* s, const CombineAr
             return 0;
         }
         s->mir_part_bytes = part_bytes;
+        // (the kernel writes every element the finishing kernel reads; zeros only so that a profiling launch that leaves the
+        //  store out -- mirror_ablate -- works on finite numbers)
+        HIPCHK(ctx, hipMemsetAsync(s->mir_part, 0, part_bytes, ctx->stream));
     }
-    if (lds > 48 * 1024) {
-        static DeviceOnce attr[6];
+    {
+        // once per device and kernel, to the most a launch of it can ask for (eight waves), whatever this stack's wpw is: a
+        // stack with fewer waves per workgroup may come first
+        static DeviceOnce attr[9];
         if (attr[slot].needed(ctx->device)) {
-            HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            const size_t most = std::min(((size_t)2 * 8 + 2) * 16 * 32 * sizeof(double2), (size_t)ctx->lds_per_block);
+            HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
             attr[slot].done(ctx->device);
         }
     }

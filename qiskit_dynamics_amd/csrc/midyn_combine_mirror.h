@@ -20,7 +20,9 @@
 // cost on rhs_combine_kernel -- and 2 x 2 x 8 vector FMAs for the two applications (the same number as before).
 //
 // Workgroup: wpw (8 where the stack has that many L row groups) waves, wave w owns L row group (set * wpw + w) and the SAME 32
-// instance columns; they walk the union of their kk block lists in one order and meet at one barrier per 16-column block.  The partial sums of the U rows of a set go
+// instance columns; they walk the union of their kk block lists in one order and meet at one barrier per 16-column block.
+// The 16 state rows y[U block] of a block, the same for all of them, are loaded once per workgroup, one block ahead, into LDS
+// (dynamic LDS: partial sums 2 x wpw x 8 KB, then this stage input 2 x 8 KB).  The partial sums of the U rows of a set go
 // to part[set][u][col] for the U blocks of its walk only; mirror_finish_kernel adds, in a fixed set order, the sets whose walk
 // covers the row's U block (cover[set][U block], built with the walks; no atomics: results are the same from run to run) and
 // runs the epilogue of the U rows.  A U row that no set covers gets the epilogue of a zero contraction.
@@ -56,14 +58,62 @@ __device__ __forceinline__ double swap_sum16(double x, double y) {
     return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
 }
 
-template <int NRE4, int NIM4>
-__global__ __launch_bounds__(512, 2) void combine_mirror_kernel(const MirrorArgs m) {
+// The fragment ring of a variant: its stages, and how many kk steps ahead of its MFMAs a step's fragments are loaded.  Four
+// stages close inside the four steps of the rolled j4 body without register moves; two steps ahead keep three of them live (a
+// third step ahead spills in <0, 2>).  The variants with more than two plane groups have no registers for more than two stages.
+constexpr int mirror_ring_depth(int nre4, int nim4) { return nre4 + nim4 <= 2 ? 4 : 2; }
+constexpr int mirror_ring_ahead(int nre4, int nim4) { return nre4 + nim4 <= 2 ? 2 : 1; }
+
+// The sum over the waves of a workgroup of a block's transposed partials (buf[w][16 kk][32 instances]), in wave order
+// (buf[0] + buf[1] + ..): every wave sums 512 / (waves) elements and stores them to the rows of `part` that start at pout.
+// mirror_wave_sum<WP>: WP a compile-time count, all reads of an element issued before the first add (one LDS round trip in
+// place of WP; WP double2 registers: used with eight waves by the variants that have them).  mirror_wave_sum_any: any count,
+// a read per add.
+template <int WP>
+__device__ __forceinline__ void mirror_wave_sum(const double2* buf, double2* pout, int ldb, int wave, int lane) {
+#pragma unroll
+    for (int i = 0; i < 512 / WP; i += 64) {
+        const int el = wave * (512 / WP) + i + lane;
+        double2 v[WP];
+#pragma unroll
+        for (int w = 0; w < WP; ++w) v[w] = buf[(unsigned)(w * 16 * 32 + el)];
+        double2 s = v[0];
+#pragma unroll
+        for (int w = 1; w < WP; ++w) {
+            s.x += v[w].x;
+            s.y += v[w].y;
+        }
+        pout[(size_t)(el >> 5) * ldb + (el & 31)] = s;
+    }
+}
+
+__device__ __forceinline__ void mirror_wave_sum_any(const double2* buf, double2* pout, int ldb, int wave, int lane, int wpw) {
+    const int per_wave = 512 / wpw;
+#pragma clang loop unroll(disable)
+    for (int i = 0; i < per_wave; i += 64) {
+        const int el = wave * per_wave + i + lane;
+        double2 s = buf[(unsigned)el];
+        for (int w = 1; w < wpw; ++w) {
+            const double2 v = buf[(unsigned)(w * 16 * 32 + el)];
+            s.x += v.x;
+            s.y += v.y;
+        }
+        pout[(size_t)(el >> 5) * ldb + (el & 31)] = s;
+    }
+}
+
+// The body of combine_mirror_kernel<NRE4, NIM4> (ABL = 0).  ABL != 0 is profiling only (mirror_probe_kernel, ctx option
+// mirror_ablate; results wrong): bit 0 = every step re-uses the fragments loaded for the first step of the launch (no global
+// loads in the kk loop; the operands pass through an empty asm per step, so the combination stays in the loop), bit 1 = no
+// phase behind the barrier (no cross-wave sum, no store of the partial sums).
+template <int NRE4, int NIM4, int ABL>
+__device__ __forceinline__ void combine_mirror_body(const MirrorArgs& m) {
     constexpr int NQ = NRE4 + NIM4, RT = 2, NG = 2;
     constexpr bool RE = NRE4 > 0, IM = NIM4 > 0;
     static_assert(combine_groups_ok(NRE4, NIM4), "plane groups");
     const CombineArgs& a = m.c;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    double2* const lds = reinterpret_cast<double2*>(smem_raw);      // [2][wpw][16 kk][32 instances]
+    double2* const lds = reinterpret_cast<double2*>(smem_raw);      // partials [2][wpw][16 kk][32 instances], then the stage input
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int set = blockIdx.x % m.nsets;
@@ -101,23 +151,45 @@ __global__ __launch_bounds__(512, 2) void combine_mirror_kernel(const MirrorArgs
             for (int g = 0; g < NG; ++g)
                 yl[t][r][g] = yb[(size_t)(rg * CMB_ROWS + 16 * t + lq + 4 * r) * a.ldb + (unsigned)(16 * g + lb)];
 
-    double afr[2][RT][NQ];
-    double2 yv[2][NG];
-    // loads of step k16 of the block (fragment entry ent, kk block kb) into buffer b
-    auto load = [&](int ent, int kb, int k16, int b) {
+    // The fragments run through a register ring of DEPTH stages: a step's loads are issued AHEAD steps before its MFMAs.
+    // The 16 state rows y[U block] of a block are the same for every wave of the workgroup: they reach LDS once per
+    // workgroup, one block ahead (each wave loads one pair of rows at the start of the block before and stores it ahead of that
+    // block's barrier, which publishes it: the stage-input buffer of the other parity was last read before the barrier of the
+    // block before), and a step reads its row from there (the four lane rows read the same address: a broadcast).
+    constexpr int DEPTH = mirror_ring_depth(NRE4, NIM4), AHEAD = mirror_ring_ahead(NRE4, NIM4);
+    double afr[DEPTH][RT][NQ];
+    double2 yv[NG];
+    // fragment loads of step k16 of the block (fragment entry ent) into stage b
+    auto load = [&](int ent, int k16, int b, bool first = false) {
+        if ((ABL & 1) && !first) {
+#pragma unroll
+            for (int t = 0; t < RT; ++t)
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) asm volatile("" : "+v"(afr[0][t][q]));
+            __builtin_amdgcn_sched_barrier(0);
+            return;
+        }
         const double* __restrict__ fn = a.frags + ((size_t)ent * 16 + k16) * (RT * NQ * 64);
 #pragma unroll
         for (int t = 0; t < RT; ++t)
 #pragma unroll
             for (int q = 0; q < NQ; ++q) afr[b][t][q] = fn[(unsigned)((t * NQ + q) * 64 + lane)];
-        const double2* __restrict__ yrow = yb + (size_t)(kb * 16 + k16) * a.ldb;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) yv[b][g] = yrow[(unsigned)(16 * g + lb)];
         __builtin_amdgcn_sched_barrier(0);
+    };
+    // this wave's pair of the 16 state rows of kk block kb (lanes 0-31: row 2 wave, lanes 32-63: row 2 wave + 1; slot
+    // wave * 64 + lane of a stage-input buffer); stacks with fewer than 8 waves per workgroup fill the other pairs in stage_rest
+    auto stage_load = [&](int kb, int pair) {
+        return yb[(size_t)(kb * 16 + 2 * pair + (lane >> 5)) * a.ldb + (unsigned)(lane & 31)];
+    };
+    auto stage_rest = [&](int kb, double2* ybuf) {
+        for (int pair = wave + m.wpw; pair < 8; pair += m.wpw) ybuf[(unsigned)(pair * 64 + lane)] = stage_load(kb, pair);
     };
     // transposed partials of two kk steps, per instance group: this lane's 8 rows summed
     double tre[2][NG], tim[2][NG];
-    auto compute = [&](int b, int kq) {
+    auto compute = [&](int bb, int kq, const double2* yrow) {
+        const int b = (ABL & 1) ? 0 : bb;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) yv[g] = yrow[(unsigned)(16 * g + lb)];
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
             tre[kq][g] = 0.0;
@@ -138,8 +210,8 @@ __global__ __launch_bounds__(512, 2) void combine_mirror_kernel(const MirrorArgs
                 for (int g = 0; g < NG; ++g)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        ore[t][g][r] = fma(gre[g][r], yv[b][g].x, ore[t][g][r]);
-                        oim[t][g][r] = fma(gre[g][r], yv[b][g].y, oim[t][g][r]);
+                        ore[t][g][r] = fma(gre[g][r], yv[g].x, ore[t][g][r]);
+                        oim[t][g][r] = fma(gre[g][r], yv[g].y, oim[t][g][r]);
                         tre[kq][g] = fma(-gre[g][r], yl[t][r][g].x, tre[kq][g]);
                         tim[kq][g] = fma(-gre[g][r], yl[t][r][g].y, tim[kq][g]);
                     }
@@ -157,8 +229,8 @@ __global__ __launch_bounds__(512, 2) void combine_mirror_kernel(const MirrorArgs
                 for (int g = 0; g < NG; ++g)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        ore[t][g][r] = fma(-gim[g][r], yv[b][g].y, ore[t][g][r]);
-                        oim[t][g][r] = fma(gim[g][r], yv[b][g].x, oim[t][g][r]);
+                        ore[t][g][r] = fma(-gim[g][r], yv[g].y, ore[t][g][r]);
+                        oim[t][g][r] = fma(gim[g][r], yv[g].x, oim[t][g][r]);
                         tre[kq][g] = fma(-gim[g][r], yl[t][r][g].y, tre[kq][g]);
                         tim[kq][g] = fma(gim[g][r], yl[t][r][g].x, tim[kq][g]);
                     }
@@ -166,8 +238,15 @@ __global__ __launch_bounds__(512, 2) void combine_mirror_kernel(const MirrorArgs
         }
     };
 
+    // the cross-wave sum of a block's transposed partials (in buf) and their store to the rows of U block kb of `part`
+    auto wave_sum = [&](const double2* buf, int kb) {
+        if (ABL & 2) return;
+        double2* const pout = m.part + ((size_t)set * m.half + (kb * 16 - m.half)) * a.ldb + col0;
+        if (NQ <= 2 && m.wpw == 8) mirror_wave_sum<8>(buf, pout, a.ldb, wave, lane);
+        else mirror_wave_sum_any(buf, pout, a.ldb, wave, lane, m.wpw);
+    };
     const int p0 = m.set_ptr[set], p1 = m.set_ptr[set + 1];
-    const int per_wave = (16 * 32) / m.wpw;             // elements of a block each wave sums over the workgroup
+    double2* const ylds = lds + (size_t)2 * m.wpw * (16 * 32);      // stage input: [2][16 kk][32 instances]
     if (p1 > p0) {
         // the walk (at most 64 blocks: stack_mirror_layout) in lane (position - p0) of two registers, read with v_readlane (loads
         // of the next block's entry inside the loop are vector loads -- the loop stores -- and drained the look-ahead loads)
@@ -175,35 +254,45 @@ __global__ __launch_bounds__(512, 2) void combine_mirror_kernel(const MirrorArgs
         const int walk = m.set_ent[pl * m.wpw + wave];
         int ent_c = __builtin_amdgcn_readlane(walk, 0), kb_c = ent_c & 4095;
         ent_c >>= 12;
-        load(ent_c, kb_c, 0, 0);
+#pragma unroll
+        for (int k = 0; k < AHEAD; ++k) load(ent_c, k, k, k == 0);
+        // the first block's state rows: the only ones not loaded a block ahead
+        ylds[(unsigned)(wave * 64 + lane)] = stage_load(kb_c, wave);
+        stage_rest(kb_c, ylds);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
         for (int pos = p0; pos < p1; ++pos) {
             // the next block's entry (the look-ahead past the last block re-reads the last one)
             const int pn = (pos + 1 < p1 ? pos + 1 : pos) - p0;
             const int wn = __builtin_amdgcn_readlane(walk, pn), ent_n = wn >> 12, kb_n = wn & 4095;
-            double2* const buf = lds + (size_t)((pos - p0) & 1) * (m.wpw * 16 * 32);
+            const int par = (pos - p0) & 1;
+            double2* const buf = lds + (size_t)par * (m.wpw * 16 * 32);
+            const double2* const ycur = ylds + par * (16 * 32);
+            const double2 ynext = stage_load(kb_n, wave);
 #pragma clang loop unroll(disable)
             for (int j4 = 0; j4 < 4; ++j4) {
                 // reduce-scatter over the 4 lane rows, a pair of steps at a time: lanes 0-31 keep the first step of a pair,
                 // lanes 32-63 the second (h[k]: pair k of the quarter); then even lane rows keep pair 0, odd ones pair 1
                 double h[2][NG][2];
-                load(ent_c, kb_c, 4 * j4 + 1, 1);
-                compute(0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                load(ent_c, kb_c, 4 * j4 + 2, 0);
-                compute(1, 1);
-                __builtin_amdgcn_sched_barrier(0);
+                const bool last = j4 == 3;
+                // step s of the quarter: the loads of step s + AHEAD (past the block's 16 steps: the next block's), then its MFMAs
+                auto step = [&](auto S) {
+                    constexpr int s_ = decltype(S)::value;
+                    const bool nx = last && s_ + AHEAD >= 4;
+                    load(nx ? ent_n : ent_c, nx ? s_ + AHEAD - 4 : 4 * j4 + s_ + AHEAD, (s_ + AHEAD) % DEPTH);
+                    compute(s_ % DEPTH, s_ & 1, ycur + (4 * j4 + s_) * 32);
+                    __builtin_amdgcn_sched_barrier(0);
+                };
+                step(std::integral_constant<int, 0>{});
+                step(std::integral_constant<int, 1>{});
 #pragma unroll
                 for (int g = 0; g < NG; ++g) {
                     h[0][g][0] = swap_sum32(tre[0][g], tre[1][g]);
                     h[0][g][1] = swap_sum32(tim[0][g], tim[1][g]);
                 }
-                load(ent_c, kb_c, 4 * j4 + 3, 1);
-                compute(0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                const bool last = j4 == 3;
-                load(last ? ent_n : ent_c, last ? kb_n : kb_c, last ? 0 : 4 * j4 + 4, 0);
-                compute(1, 1);
-                __builtin_amdgcn_sched_barrier(0);
+                step(std::integral_constant<int, 2>{});
+                step(std::integral_constant<int, 3>{});
 #pragma unroll
                 for (int g = 0; g < NG; ++g) {
                     h[1][g][0] = swap_sum32(tre[0][g], tre[1][g]);
@@ -218,22 +307,15 @@ __global__ __launch_bounds__(512, 2) void combine_mirror_kernel(const MirrorArgs
                     buf[(unsigned)((wave * 16 + kkl) * 32 + 16 * g + lb)] = make_double2(sr, si);
                 }
             }
-            // one barrier per block: the other buffer was last read before the barrier of the previous block
+            // the next block's state rows, then one barrier per block: the other buffers were last read before the barrier of
+            // the previous block
+            double2* const ynb = ylds + (par ^ 1) * (16 * 32);
+            ynb[(unsigned)(wave * 64 + lane)] = ynext;
+            stage_rest(kb_n, ynb);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-#pragma clang loop unroll(disable)
-            for (int i = 0; i < per_wave; i += 64) {
-                const int el = wave * per_wave + i + lane;
-                double2 s = buf[(unsigned)el];
-                for (int w = 1; w < m.wpw; ++w) {
-                    const double2 v = buf[(unsigned)(w * 16 * 32 + el)];
-                    s.x += v.x;
-                    s.y += v.y;
-                }
-                const int u = kb_c * 16 + (el >> 5) - m.half;
-                m.part[((size_t)set * m.half + u) * a.ldb + col0 + (el & 31)] = s;
-            }
+            wave_sum(buf, kb_c);
             ent_c = ent_n;
             kb_c = kb_n;
         }
@@ -243,6 +325,17 @@ __global__ __launch_bounds__(512, 2) void combine_mirror_kernel(const MirrorArgs
     int lane_t;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_t));
     store_tile<RT, NG>(a.epi, rg * CMB_ROWS + (lane_t >> 4), col0 + (lane_t & 15), ore, oim);
+}
+
+template <int NRE4, int NIM4>
+__global__ __launch_bounds__(512, 2) void combine_mirror_kernel(const MirrorArgs m) {
+    combine_mirror_body<NRE4, NIM4, 0>(m);
+}
+
+// profiling only (ctx option mirror_ablate = ABL; results wrong): the <0, 2> body with parts of it taken out
+template <int ABL>
+__global__ __launch_bounds__(512, 2) void mirror_probe_kernel(const MirrorArgs m) {
+    combine_mirror_body<0, 2, ABL>(m);
 }
 
 // The U rows: the partial sums of the sets whose walk covers the row's U block, added in set order (part[0] + part[1] + ..;
@@ -300,6 +393,9 @@ MIDYN_GLOBAL __launch_bounds__(256) void mirror_defect_kernel(const double2* A, 
 #endif
 #define MIDYN_X(R_, I_) MIDYN_COMBINE_MIRROR_EXTERN template __global__ void combine_mirror_kernel<R_, I_>(const MirrorArgs);
 MIDYN_X(0, 1) MIDYN_X(0, 2) MIDYN_X(1, 0) MIDYN_X(2, 0) MIDYN_X(1, 1) MIDYN_X(2, 2)
+#undef MIDYN_X
+#define MIDYN_X(A_) MIDYN_COMBINE_MIRROR_EXTERN template __global__ void mirror_probe_kernel<A_>(const MirrorArgs);
+MIDYN_X(1) MIDYN_X(2) MIDYN_X(3)
 #undef MIDYN_X
 #define MIDYN_X(E_) MIDYN_COMBINE_MIRROR_EXTERN template __global__ void mirror_finish_kernel<E_>(const double2*, const int*, int, int, int, Epilogue);
 MIDYN_X(EPI_RHS) MIDYN_X(EPI_RK1) MIDYN_X(EPI_RK2) MIDYN_X(EPI_RK3) MIDYN_X(EPI_RK4)

@@ -76,6 +76,9 @@ struct midyn_ctx {
     double last_mirror[2] = {0, 0};   // (1 if the last combine launch was mirrored, the stack's mirror defect in units of epsilon)
     int combine_ablate = 0;      // profiling only (results wrong): 1 = rhs_combine_kernel stores its result and nothing else (no fused RK4 /
                                  // series stage: none of the epilogue's reads, one of its two writes) -- what the epilogue of a launch costs
+    int mirror_ablate = 0;       // profiling only (results wrong): mirror_probe_kernel<N> in place of combine_mirror_kernel<0, 2> -- 1 = no global
+                                 // loads in the kk loop (the first step's operands every step), 2 = no phase behind the block barrier (no
+                                 // cross-wave sum, no store of the partial sums), 3 = both
     int combine_occupancy = 2;   // waves per SIMD the workgroup shape of a small sweep aims at (list splits up to 8); 1: one wave, splits up to 4
     int combine_sweep = 1;       // RK4 sweeps of small dense systems (n_pad <= 256): the whole solve in one launch, 16 instances per
                                  // workgroup (midyn_combine_sweep.h); 1: where it is faster than a launch per stage, 2: wherever it
@@ -316,7 +319,7 @@ extern "C" int midyn_ctx_synchronize(midyn_ctx* ctx) {
     X(ell_sweep_packed) X(multi_stream) X(expm_action) X(split_k) X(combine_first) X(plane_kernel) X(pair_launch)        \
     X(splitk_inlaunch)
 #define MIDYN_INT_OPTIONS(X)                                                                                             \
-    X(ell_sweep_duo) X(ell_sweep_flip) X(sparse_bm) X(chebyshev) X(force_tile) X(ablate) X(stream_variant) X(ell_sweep_split) X(combine) X(combine_mirror) X(combine_occupancy) X(combine_ablate) \
+    X(ell_sweep_duo) X(ell_sweep_flip) X(sparse_bm) X(chebyshev) X(force_tile) X(ablate) X(stream_variant) X(ell_sweep_split) X(combine) X(combine_mirror) X(combine_occupancy) X(combine_ablate) X(mirror_ablate) \
     X(combine_sweep) X(expm_degree) X(krylov) X(force_splits) X(complex_3m) X(cheb_tail) X(expm_direct_out) X(exchange_protocol) X(expansion_pack) X(expm_plan_cache) \
     X(gentable_chain) X(gentable_chunk)
 
