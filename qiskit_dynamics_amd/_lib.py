@@ -36,6 +36,10 @@ ABI_SYMBOLS = [
 GENTABLE_SYMBOLS = [
     "midyn_gentable_create", "midyn_gentable_push", "midyn_gentable_info", "midyn_gentable_finish", "midyn_gentable_destroy",
 ]
+# every symbol include/midyn_spmv.h declares (models with scipy.sparse operators; tests/test_spmv_host.py)
+SPMV_SYMBOLS = [
+    "midyn_spmv_create", "midyn_spmv_destroy", "midyn_spmv_info", "midyn_spmv_eval_rhs", "midyn_spmv_rk4_solve",
+]
 
 
 class DynamicsError(Exception):
@@ -197,7 +201,12 @@ def load():
         lib.midyn_gentable_info.argtypes = [_vp, _vp]
         lib.midyn_gentable_finish.argtypes = [_vp, _vp]
         lib.midyn_gentable_destroy.argtypes = [_vp]
-        for name in ABI_SYMBOLS + GENTABLE_SYMBOLS:
+        lib.midyn_spmv_create.argtypes = [_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, P(_vp)]
+        lib.midyn_spmv_destroy.argtypes = [_vp]
+        lib.midyn_spmv_info.argtypes = [_vp, P(_cll)]
+        lib.midyn_spmv_eval_rhs.argtypes = [_vp, _vp, _cd, _vp, _ci, _vp]
+        lib.midyn_spmv_rk4_solve.argtypes = [_vp, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _ci, _vp, _ci, _vp]
+        for name in ABI_SYMBOLS + GENTABLE_SYMBOLS + SPMV_SYMBOLS:
             if name != "midyn_last_error":
                 getattr(lib, name).restype = _ci
         _lib = lib
@@ -690,6 +699,140 @@ class Stack:
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle and self.ctx.handle:
             self.ctx.lib.midyn_stack_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pylint: disable=broad-except
+            pass
+
+
+def pack_ell(n, static, ops):
+    """Merge the static part and the ``k`` operators (``scipy.sparse`` matrices or ``None`` / an empty list) into ONE padded
+    row structure (include/midyn_spmv.h): ``W`` slots per row, ``W`` = the largest number of entries a row has over all
+    operators together.  A slot is (column, operator index, value); operator index ``k`` is the static part (coefficient 1).
+    The entries of a row are grouped by operator index (ascending, the static part last, columns ascending inside a group);
+    duplicate entries are summed and stored zeros dropped; unused slots are (col = row, op = k, val = 0).  Pure NumPy / SciPy.
+
+    Returns a dict: ``n``, ``k``, ``width``, ``n_pad`` and two images of the same structure, row major ``cols`` / ``ops`` /
+    ``vals`` of shape (n, W) and slot major ``cols_t`` / ``ops_t`` / ``vals_t`` of shape (W, n_pad) (rows of 64)."""
+    from scipy import sparse
+
+    n = int(n)
+    ops = [] if ops is None else list(ops)
+    k = len(ops)
+    if n <= 0:
+        raise DynamicsError("pack_ell: the dimension must be positive")
+    rows_l, cols_l, ops_l, vals_l = [], [], [], []
+    for idx, mat in [(j, a) for j, a in enumerate(ops)] + ([] if static is None else [(k, static)]):
+        if not sparse.issparse(mat):
+            mat = np.asarray(mat)
+            if mat.ndim != 2:
+                raise DynamicsError("pack_ell: operators must be square matrices")
+        if mat.shape != (n, n):
+            raise DynamicsError(f"pack_ell: operator of shape {tuple(mat.shape)} where ({n}, {n}) is required")
+        try:
+            coo = sparse.coo_matrix(mat, dtype=np.complex128)
+        except ValueError as exc:       # (scipy's own check of the index arrays)
+            raise DynamicsError(f"pack_ell: {exc}") from None
+        if coo.nnz and (coo.row.min() < 0 or coo.col.min() < 0 or coo.row.max() >= n or coo.col.max() >= n):
+            raise DynamicsError("pack_ell: an index lies outside [0, n)")
+        coo.sum_duplicates()
+        keep = coo.data != 0
+        rows_l.append(coo.row[keep].astype(np.int64))
+        cols_l.append(coo.col[keep].astype(np.int64))
+        vals_l.append(coo.data[keep])
+        ops_l.append(np.full(int(keep.sum()), idx, dtype=np.int64))
+    if rows_l:
+        rows, cols = np.concatenate(rows_l), np.concatenate(cols_l)
+        opi, vals = np.concatenate(ops_l), np.concatenate(vals_l)
+    else:
+        rows = cols = opi = np.zeros(0, dtype=np.int64)
+        vals = np.zeros(0, dtype=np.complex128)
+    order = np.lexsort((cols, opi, rows))        # by row, then operator index, then column
+    rows, cols, opi, vals = rows[order], cols[order], opi[order], vals[order]
+    counts = np.bincount(rows, minlength=n)
+    width = int(counts.max()) if rows.size else 0
+    n_pad = -(-n // 64) * 64
+    out_c = np.repeat(np.arange(n, dtype=np.int32)[:, None], width, axis=1)
+    out_o = np.full((n, width), k, dtype=np.int32)
+    out_v = np.zeros((n, width), dtype=np.complex128)
+    slot = np.arange(rows.size) - (np.cumsum(counts) - counts)[rows]
+    out_c[rows, slot] = cols
+    out_o[rows, slot] = opi
+    out_v[rows, slot] = vals
+    cols_t = np.zeros((width, n_pad), dtype=np.int32)
+    cols_t[:, :] = np.minimum(np.arange(n_pad, dtype=np.int32), n - 1)[None, :]
+    ops_t = np.full((width, n_pad), k, dtype=np.int32)
+    vals_t = np.zeros((width, n_pad), dtype=np.complex128)
+    cols_t[:, :n], ops_t[:, :n], vals_t[:, :n] = out_c.T, out_o.T, out_v.T
+    return dict(n=n, k=k, width=width, n_pad=n_pad, cols=np.ascontiguousarray(out_c), ops=np.ascontiguousarray(out_o),
+                vals=np.ascontiguousarray(out_v), cols_t=cols_t, ops_t=ops_t, vals_t=vals_t)
+
+
+class SpmvStack:
+    """Device-resident sparse operator stack (``midyn_spmv``, include/midyn_spmv.h) made from ``pack_ell``'s structure.
+    ``eval_rhs`` and ``rk4_solve`` take and return what ``Stack.eval_rhs`` / ``Stack.rk4_solve`` do."""
+
+    def __init__(self, ctx: Context, n, k, packed, frame_im):
+        self.ctx = ctx
+        self.handle = None
+        if packed["n"] != n or packed["k"] != k:
+            raise DynamicsError("SpmvStack: the packed structure was made for another dimension or operator count")
+        cols, ops, vals = i32(packed["cols"]), i32(packed["ops"]), c128(packed["vals"])
+        width = int(packed["width"])
+        if cols.shape != (n, width) or ops.shape != (n, width) or vals.shape != (n, width):
+            raise DynamicsError("SpmvStack: cols / ops / vals must have the shape (n, width)")
+        fr = None if frame_im is None else f64(frame_im)
+        if fr is not None and fr.shape != (n,):
+            raise DynamicsError("SpmvStack: frame_im must have n entries")
+        h = _vp()
+        ctx.check(ctx.lib.midyn_spmv_create(ctx.handle, int(n), int(k), width, _ptr(cols), _ptr(ops), _ptr(vals), _ptr(fr),
+                                            ctypes.byref(h)))
+        self.handle = h
+        info = (ctypes.c_longlong * 7)()
+        ctx.check(ctx.lib.midyn_spmv_info(h, info))
+        self.n, self.n_pad, self.k, self.width, self.has_frame, self.nnz, self.device_bytes = [int(x) for x in info]
+        self.n_api = self.n
+
+    def eval_rhs(self, coeffs, t, y):
+        y = c128(y)
+        if y.shape[0] != self.n or y.ndim > 2:
+            raise DynamicsError("state has the wrong shape")
+        m = 1 if y.ndim == 1 else y.shape[1]
+        out = np.empty_like(y)
+        c = None if self.k == 0 else f64(coeffs)
+        if c is not None and c.shape != (self.k,):
+            raise DynamicsError("coefficient vector has the wrong length")
+        self.ctx.check(self.ctx.lib.midyn_spmv_eval_rhs(self.handle, _ptr(c), float(t), _ptr(y), m, _ptr(out)))
+        return out
+
+    def rk4_solve(self, times, table, step_rows, step_h, step_save, n_save, y0, batch, y0_shared):
+        """y0: (n,m) if y0_shared else (B,n,m).  Returns (B, P, n, m)."""
+        times = f64(times)
+        r = times.shape[0]
+        if self.k > 0:
+            if not isinstance(table, SignalTable):
+                table = f64(table)
+            if table.shape != (batch, r, self.k):
+                raise DynamicsError(f"coefficient table must be (B,R,k)={(batch, r, self.k)}, got {table.shape}")
+        else:
+            table = None
+        step_rows, step_h, step_save = i32(step_rows).reshape(-1, 3), f64(step_h), i32(step_save)
+        y0 = c128(y0)
+        if y0.shape[:-1] != ((self.n,) if y0_shared else (batch, self.n)):
+            raise DynamicsError("initial state has the wrong shape")
+        m = y0.shape[-1]
+        out = result_array((batch, n_save, self.n, m))
+        self.ctx.check(self.ctx.lib.midyn_spmv_rk4_solve(
+            self.handle, batch, m, r, _ptr(times), _ptr(table), step_rows.shape[0], _ptr(step_rows), _ptr(step_h),
+            _ptr(step_save), n_save, _ptr(y0), int(bool(y0_shared)), _ptr(out)))
+        return out
+
+    def close(self):
+        if getattr(self, "handle", None) is not None and self.handle and self.ctx.handle:
+            self.ctx.lib.midyn_spmv_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

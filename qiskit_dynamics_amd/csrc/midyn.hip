@@ -24,12 +24,14 @@
 
 #include "../../include/midyn.h"
 #include "../../include/midyn_gentable.h"
+#include "../../include/midyn_spmv.h"
 #include "midyn_kernels.h"
 #include "midyn_resident.h"
 #include "midyn_flip.h"
 #include "midyn_combine.h"
 #include "midyn_combine_mirror.h"
 #include "midyn_combine_sweep.h"
+#include "midyn_spmv.h"
 
 using namespace midyn;
 
@@ -44,6 +46,7 @@ using namespace midyn;
 #include "midyn_action.inc"
 #include "midyn_parallel.inc"
 #include "midyn_gentable.inc"
+#include "midyn_spmv.inc"
 #include "midyn_expansion.inc"
 #include "midyn_lindblad.inc"
 #include "midyn_microbench.inc"

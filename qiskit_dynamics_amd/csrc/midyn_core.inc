@@ -4,13 +4,14 @@
 // -------------------------------------------------------------------------------------------------
 static thread_local std::string g_last_error;
 
-enum KClass { KC_STREAM = 0, KC_RHS_GEMM, KC_ZGEMM, KC_GEN, KC_ELEM, KC_BLOCKS, KC_BLOCKS_GEMM, KC_RESIDENT, KC_COMBINE, KC_GEN_CHAIN, KC_MIRROR_FINISH, KC_COUNT };
+enum KClass { KC_STREAM = 0, KC_RHS_GEMM, KC_ZGEMM, KC_GEN, KC_ELEM, KC_BLOCKS, KC_BLOCKS_GEMM, KC_RESIDENT, KC_COMBINE, KC_GEN_CHAIN, KC_MIRROR_FINISH, KC_SPMV, KC_COUNT };
 static const char* kclass_names[KC_COUNT] = {"rhs_stream", "rhs_gemm", "zgemm", "gen_eval", "elementwise",
                                              "rhs_blocks", "rhs_blocks_gemm",   // block-sparse routes
                                              "rk4_resident",   // whole step ranges of one trajectory in one launch
                                              "rhs_combine",   // sweeps: combine (MFMA over the operator planes) + apply (midyn_combine.h)
                                              "gen_chain",     // callable generators: a chunk of step propagators applied in one launch (midyn_gentable.inc)
-                                             "mirror_finish"};   // mirrored combine: sum of the U-row partials + their epilogue (midyn_combine_mirror.h)
+                                             "mirror_finish",   // mirrored combine: sum of the U-row partials + their epilogue (midyn_combine_mirror.h)
+                                             "rhs_spmv"};       // sparse operators: the stage launches of the gather kernels (midyn_spmv.h)
 
 struct EventPair {
     hipEvent_t a, b;
@@ -47,6 +48,7 @@ struct midyn_ctx {
     int expm_plan_cache = 1;   // one-shot midyn_expm_solve on the sweep route keeps its plan in the stack (midyn_sweep_plan.inc); 0: made and destroyed per call
     int gentable_chain = 1;    // midyn_gentable, sequential route, n_pad <= 128 and m <= 32: gen_chain_kernel (one launch per chunk); 0: a zgemm per step
     int gentable_chunk = 0;    // midyn_gentable: > 0 caps the steps per chunk
+    int spmv_lanes = 0;        // midyn_spmv: lane mapping of the gather kernels: 1 = (row, column) pairs, 2 = 64 state columns of one row, 0 = by the column count
     double last_gentable[4] = {0, 0, 0, 0};   // last midyn_gentable solve: chunks, steps in the largest chunk, pinned staging bytes, device raw-row bytes
     int last_plan_cache = 0;   // (1: the last one-shot sweep solve found its plan in the stack; counter "expm_plan_cache")
     unsigned long long options_epoch = 1;      // counts midyn_ctx_set_option calls: cached plans are tied to the options they were made under
@@ -321,7 +323,7 @@ extern "C" int midyn_ctx_synchronize(midyn_ctx* ctx) {
 #define MIDYN_INT_OPTIONS(X)                                                                                             \
     X(ell_sweep_duo) X(ell_sweep_flip) X(sparse_bm) X(chebyshev) X(force_tile) X(ablate) X(stream_variant) X(ell_sweep_split) X(combine) X(combine_mirror) X(combine_occupancy) X(combine_ablate) X(mirror_ablate) \
     X(combine_sweep) X(expm_degree) X(krylov) X(force_splits) X(complex_3m) X(cheb_tail) X(expm_direct_out) X(exchange_protocol) X(expansion_pack) X(expm_plan_cache) \
-    X(gentable_chain) X(gentable_chunk)
+    X(gentable_chain) X(gentable_chunk) X(spmv_lanes)
 
 extern "C" int midyn_ctx_set_option(midyn_ctx* ctx, const char* name, long long value) {
     if (!ctx || !name) return fail(ctx, "midyn_ctx_set_option: NULL argument");

@@ -4,8 +4,13 @@ Drop-in surface for the reference's ``GeneratorModel`` (models/generator_model.p
 ``HamiltonianModel`` (models/hamiltonian_model.py:31-150) and ``LindbladModel``
 (models/lindblad_model.py:38-538): same constructor keywords, ``evaluate(t)``, ``evaluate_rhs(t,
 y)``, ``__call__``, ``signals`` setter, ``in_frame_basis``, ``dim``, ``rotating_frame`` and
-operator getters.  ``array_library`` accepts ``None`` or ``"hip"``; this package has exactly one
+operator getters.  ``array_library`` accepts ``None``, ``"hip"`` or ``"scipy_sparse"``; this package has exactly one
 compute path (the HIP library) and raises if it is unavailable.
+
+``array_library="scipy_sparse"`` (also chosen when ``array_library`` is None and an operator is a ``scipy.sparse``
+matrix; models/generator_model.py:332-390 of the reference): the operators stay sparse from the constructor to the device
+(``_lib.pack_ell`` -> ``_lib.SpmvStack``), the rotating frame must be diagonal, ``evaluate`` returns a ``csr_matrix``
+assembled on the host and ``evaluate_rhs`` / the RK4 solvers run on the gather kernels.
 
 Build time (host, once): -iH, frame diagonalisation, U^dagger . U of the operator stack, Kronecker
 superoperators for the vectorised Lindblad model; the resulting frame-basis stack is uploaded once
@@ -23,14 +28,16 @@ from ._lib import DynamicsError
 from .rotating_frame import RotatingFrame
 from .signals import Signal, SignalList
 
-_ACCEPTED_LIBS = (None, "hip")
+SPARSE_LIB = "scipy_sparse"
+_ACCEPTED_LIBS = (None, "hip", SPARSE_LIB)
 
 
 def _check_library(array_library):
     if array_library not in _ACCEPTED_LIBS:
         raise DynamicsError(
             f"array_library={array_library!r} is not available in qiskit_dynamics_amd; the only "
-            "compute path is array_library='hip' (libmidyn on MI355X).")
+            "compute path is array_library='hip' (libmidyn on MI355X), with array_library='scipy_sparse' for operators "
+            "given as scipy.sparse matrices.")
 
 
 def is_hermitian(operator, tol: float = 1e-10) -> bool:
@@ -51,6 +58,81 @@ def is_hermitian(operator, tol: float = 1e-10) -> bool:
             if not total < tol * tol:               # also leaves on NaN
                 return False
     return True
+
+
+def _sparse_requested(array_library, static_operator, operators) -> bool:
+    """The sparse mode: named, or (array_library None) the static operator or any operator is a scipy.sparse matrix."""
+    if array_library == SPARSE_LIB:
+        return True
+    if array_library is not None:
+        return False
+    from scipy.sparse import issparse
+
+    if issparse(static_operator) or issparse(operators):
+        return True
+    return isinstance(operators, (list, tuple)) and any(issparse(op) for op in operators)
+
+
+def _to_csr(mat, what):
+    """One square operator as a complex csr_matrix (dense input is converted)."""
+    from scipy.sparse import csr_matrix, issparse
+
+    if not issparse(mat):
+        mat = np.asarray(mat)
+        if mat.ndim != 2:
+            raise DynamicsError(f"{what} must be a square matrix")
+    if mat.shape[0] != mat.shape[1]:
+        raise DynamicsError(f"{what} must be a square matrix")
+    return csr_matrix(mat, dtype=complex)
+
+
+def _to_csr_list(operators):
+    from scipy.sparse import issparse
+
+    if issparse(operators):
+        raise DynamicsError("operators must be a list of square matrices (one scipy.sparse matrix per operator)")
+    out = [_to_csr(op, "every operator") for op in operators]
+    if len({op.shape for op in out}) > 1:
+        raise DynamicsError("operators must all have the same dimension")
+    return out
+
+
+def is_hermitian_sparse(mat, tol: float = 1e-10) -> bool:
+    """|| A - A^dagger ||_F < tol on a scipy.sparse matrix (the tolerance of ``is_hermitian``)."""
+    d = (mat - mat.conj().T).tocsr()
+    return bool(np.sqrt(float(np.sum(np.abs(d.data) ** 2))) < tol)
+
+
+def _diagonal_frame(rotating_frame):
+    """The frame of a sparse model as its 1-D diagonal (None: no frame).  Accepted: None, a 1-D array, a dense or sparse
+    matrix whose off-diagonal part is exactly zero, a RotatingFrame made from one of these."""
+    from scipy.sparse import issparse
+
+    if isinstance(rotating_frame, RotatingFrame):
+        if rotating_frame.frame_basis is None:
+            return rotating_frame.frame_operator
+        rotating_frame = rotating_frame.frame_operator
+    if rotating_frame is None:
+        return None
+    refuse = DynamicsError(
+        "array_library='scipy_sparse' needs a diagonal rotating frame (a 1-D array, or a matrix whose off-diagonal part is "
+        "exactly zero): rotating the operators into the eigenbasis of a general frame would make them dense. Give the "
+        "operators as dense arrays (array_library='hip') to use this frame.")
+    if issparse(rotating_frame):
+        from scipy.sparse import diags
+
+        if rotating_frame.shape[0] != rotating_frame.shape[1]:
+            raise refuse
+        diag = np.asarray(rotating_frame.diagonal())
+        if (rotating_frame - diags(diag)).count_nonzero():
+            raise refuse
+        return diag
+    f = np.asarray(rotating_frame)
+    if f.ndim == 1:
+        return f
+    if f.ndim != 2 or f.shape[0] != f.shape[1] or np.count_nonzero(f - np.diag(np.diagonal(f))):
+        raise refuse
+    return np.diagonal(f).copy()
 
 
 def _as_signal_list(signals, n_ops, what="Signals"):
@@ -182,6 +264,9 @@ class GeneratorModel(BaseGeneratorModel):
             raise DynamicsError(
                 f"{type(self).__name__} requires at least one of static_operator or operators to "
                 "be specified at construction.")
+        if _sparse_requested(array_library, static_operator, operators):
+            self._init_sparse(static_operator, operators, signals, rotating_frame, in_frame_basis, context)
+            return
         self._rotating_frame = RotatingFrame(rotating_frame)
         self._in_frame_basis = in_frame_basis
         frame = self._rotating_frame
@@ -236,6 +321,52 @@ class GeneratorModel(BaseGeneratorModel):
         self._signals = None
         self.signals = signals
 
+    _sparse = False
+
+    def _init_sparse(self, static_operator, operators, signals, rotating_frame, in_frame_basis, context):
+        """The sparse mode: operators as csr matrices, a diagonal frame (its basis is the identity, so the frame basis is
+        the basis the operators are given in), one padded row structure on the device."""
+        from scipy.sparse import diags
+
+        self._sparse = True
+        self.array_library = SPARSE_LIB
+        self._rotating_frame = RotatingFrame(_diagonal_frame(rotating_frame))
+        self._in_frame_basis = in_frame_basis
+        frame = self._rotating_frame
+        self._ctx = context or _lib.default_context()
+        static = None if static_operator is None else _to_csr(static_operator, "static_operator")
+        ops = None if operators is None else _to_csr_list(operators)
+        self._dim = static.shape[0] if static is not None else ops[0].shape[0]
+        if ops is not None and any(op.shape[0] != self._dim for op in ops):
+            raise DynamicsError("operators and static_operator must have the same dimension")
+        if frame.dim is not None and frame.dim != self._dim:
+            raise DynamicsError("rotating frame dimension does not match the operators")
+        if frame.frame_diag is not None:      # the frame is subtracted from the static part once, here
+            minus_frame = diags(-frame.frame_diag, format="csr", dtype=complex)
+            static = minus_frame if static is None else (static + minus_frame).tocsr()
+        self._static_fb = static
+        self._ops_fb = ops
+        packed = _lib.pack_ell(self._dim, static, ops)
+        self._stack = _lib.SpmvStack(self._ctx, self._dim, 0 if ops is None else len(ops), packed, frame.frame_diag_imag)
+        self._signals = None
+        self.signals = signals
+
+    def _evaluate_sparse(self, time):
+        """csr_matrix of the generator at ``time``, assembled on the host (not a hot path; the reference returns a sparse
+        matrix here too)."""
+        from scipy.sparse import csr_matrix, diags
+
+        coeffs = self._coefficients(time)
+        gen = csr_matrix((self._dim, self._dim), dtype=complex) if self._static_fb is None else self._static_fb
+        if self._ops_fb is not None:
+            for c, op in zip(coeffs, self._ops_fb):
+                gen = gen + c * op
+        d = self._rotating_frame.frame_diag
+        if d is not None:
+            e = np.exp(d * time)
+            gen = diags(e.conj()) @ gen @ diags(e)
+        return csr_matrix(gen)
+
     # frame diagonal seen by the device (overridden by the vectorised Lindblad model)
     def _frame_diag_imag(self):
         return self._rotating_frame.frame_diag_imag
@@ -258,15 +389,15 @@ class GeneratorModel(BaseGeneratorModel):
         self._in_frame_basis = value
 
     @property
-    def stack(self) -> "_lib.Stack":
-        """The device-resident operator stack (frame basis)."""
+    def stack(self) -> "Union[_lib.Stack, _lib.SpmvStack]":
+        """The device-resident operator stack (frame basis); an ``SpmvStack`` in the sparse mode."""
         return self._stack
 
     @property
     def static_operator(self):
         if self._static_fb is None:
             return None
-        if self._in_frame_basis:
+        if self._in_frame_basis or self._sparse:      # (sparse mode: the frame basis is the identity)
             return self._static_fb
         return self._rotating_frame.operator_out_of_frame_basis(self._static_fb)
 
@@ -274,6 +405,8 @@ class GeneratorModel(BaseGeneratorModel):
     def operators(self):
         if self._ops_fb is None:
             return None
+        if self._sparse:
+            return list(self._ops_fb)
         if self._in_frame_basis:
             return self._ops_fb
         return self._rotating_frame.operator_out_of_frame_basis(self._ops_fb)
@@ -289,7 +422,7 @@ class GeneratorModel(BaseGeneratorModel):
         elif self._ops_fb is None:
             raise DynamicsError("Signals must be None if operators is None.")
         else:
-            self._signals = _as_signal_list(signals, self._ops_fb.shape[0])
+            self._signals = _as_signal_list(signals, len(self._ops_fb))
 
     # -- evaluation -----------------------------------------------------------------------------
     def _coefficients(self, time):
@@ -304,7 +437,9 @@ class GeneratorModel(BaseGeneratorModel):
         return self._rotating_frame.frame_basis
 
     def evaluate(self, time: float):
-        """Generator matrix at ``time`` (in the rotating frame)."""
+        """Generator matrix at ``time`` (in the rotating frame); a ``scipy.sparse.csr_matrix`` in the sparse mode."""
+        if self._sparse:
+            return self._evaluate_sparse(time)
         g = self._stack.eval_generator(self._coefficients(time), time)
         basis = self._basis()
         if not self._in_frame_basis and basis is not None:
@@ -341,6 +476,22 @@ class HamiltonianModel(GeneratorModel):
             raise DynamicsError(
                 f"{type(self).__name__} requires at least one of static_operator or operators to be "
                 "specified at construction.")
+        if _sparse_requested(array_library, static_operator, operators):
+            # the sparse mode: Hermiticity on the sparse matrices, -i H as csr matrices
+            if static_operator is not None:
+                static_operator = _to_csr(static_operator, "static_operator")
+                if validate and not is_hermitian_sparse(static_operator):
+                    raise DynamicsError("HamiltonianModel static_operator must be Hermitian.")
+                static_operator = -1j * static_operator
+            if operators is not None:
+                operators = _to_csr_list(operators)
+                if validate and any(not is_hermitian_sparse(op) for op in operators):
+                    raise DynamicsError("HamiltonianModel operators must be Hermitian.")
+                operators = [-1j * op for op in operators]
+            super().__init__(static_operator=static_operator, operators=operators, signals=signals,
+                             rotating_frame=rotating_frame, in_frame_basis=in_frame_basis,
+                             array_library=SPARSE_LIB, context=context)
+            return
         dim = np.shape(static_operator if user_static else operators)[-1]
         frame_is_diagonal = rotating_frame is None or (
             isinstance(rotating_frame, RotatingFrame) and rotating_frame.frame_basis is None) or (
@@ -369,6 +520,8 @@ class HamiltonianModel(GeneratorModel):
     def static_operator(self):
         if self._static_fb is None:
             return None
+        if self._sparse:
+            return (1j * self._static_fb).tocsr()
         if self._in_frame_basis:
             return self._static_fb
         return 1j * self._rotating_frame.operator_out_of_frame_basis(self._static_fb)
@@ -377,6 +530,8 @@ class HamiltonianModel(GeneratorModel):
     def operators(self):
         if self._ops_fb is None:
             return None
+        if self._sparse:
+            return [(1j * op).tocsr() for op in self._ops_fb]
         if self._in_frame_basis:
             return 1j * self._ops_fb
         return 1j * self._rotating_frame.operator_out_of_frame_basis(self._ops_fb)
@@ -394,6 +549,12 @@ class LindbladModel(BaseGeneratorModel):
                  array_library: Optional[str] = None, vectorized: bool = False,
                  validate: bool = True, context=None):
         _check_library(array_library)
+        if array_library == SPARSE_LIB or any(
+                _sparse_requested(None, st, ops) for st, ops in ((static_hamiltonian, hamiltonian_operators),
+                                                                 (None, static_dissipators), (None, dissipator_operators))):
+            raise DynamicsError(
+                "LindbladModel does not take array_library='scipy_sparse': sparse operators are supported for GeneratorModel "
+                "and HamiltonianModel only. Give the operators as dense arrays (array_library='hip').")
         if (static_hamiltonian is None and hamiltonian_operators is None
                 and static_dissipators is None and dissipator_operators is None):
             raise DynamicsError(

@@ -238,6 +238,11 @@ class ExpansionModel:
                  context=None, **kwargs):
         if expansion_method not in ("dyson", "magnus"):
             raise DynamicsError("ExpansionModel only accepts expansion_method 'dyson' or 'magnus'.")
+        from scipy.sparse import issparse
+
+        if any(issparse(op) for op in operators):
+            raise DynamicsError("The perturbative solvers do not take scipy.sparse operators: the expansion terms are dense. "
+                                "Give the operators as dense arrays.")
         operators = np.asarray([np.asarray(getattr(op, "data", op), dtype=complex) for op in operators])
         if len(operators) != len(carrier_freqs):
             raise DynamicsError("carrier_freqs must have the same length as operators.")

@@ -7,6 +7,10 @@ list mode :556-590) restricted to the fixed-step methods of the hot path:
     method "RK4"  / "hip_RK4"        classic RK4          (fixed_step_solvers.py:43-77)
     method "scipy_expm" / "hip_expm" Magnus-1/2/3 + expm  (fixed_step_solvers.py:80-108,321-403)
 
+Models with sparse operators (``array_library="scipy_sparse"``) take "RK4" / "hip_RK4" on the gather kernels (route
+"spmv": one batched device call per group of instances) and scipy's adaptive methods with the sparse device RHS; the
+LMDE methods need dense operators and say so.
+
 A generator given as a plain Python callable ``G(t)`` (``solve_lmde`` / ``scipy_expm_solver``) runs the LMDE methods
 only: the host samples ``G`` at the times of the fixed-step schedule and streams the samples to the device, which forms
 the step propagators and applies them (``_solve_callable``; include/midyn_gentable.h).
@@ -190,7 +194,7 @@ def _signal_table(model, signals, times) -> np.ndarray:
             return model._signal_table(times)
         # the passed signals are validated and tabulated WITHOUT touching model.signals (functional path)
         return model._signal_table(times, signals if isinstance(signals, tuple) else (signals, None))
-    n_ops = 0 if model._ops_fb is None else model._ops_fb.shape[0]
+    n_ops = 0 if model._ops_fb is None else len(model._ops_fb)
     sl = model.signals if signals is None else signals
     if sl is None:
         if n_ops:
@@ -360,7 +364,13 @@ AUTO_PARALLEL_MAX_ROWS = 128
 AUTO_PARALLEL_MIN_STEPS = 256
 
 
+def _is_sparse(model) -> bool:
+    return bool(getattr(model, "_sparse", False))
+
+
 def _auto_parallel_allowed(model) -> bool:
+    if _is_sparse(model):       # the tree products are dense matrices
+        return False
     if AUTO_PARALLEL_IN_TIME == "all":
         return True
     return bool(AUTO_PARALLEL_IN_TIME) and isinstance(model, HamiltonianModel)
@@ -374,6 +384,11 @@ def _solve_batch(model, t_span, y0_list, signals_list, method, t_eval=None, max_
     if max_dt is None:
         raise DynamicsError("max_dt must be specified for fixed-step methods.")
     kind = _model_kind(model)
+    if _is_sparse(model) and method in EXPM_METHODS + EXPM_PARALLEL_METHODS + RK4_PARALLEL_METHODS:
+        raise DynamicsError(
+            f"Method {method} is not available for a model with array_library='scipy_sparse': matrix exponentials and "
+            "step propagators are dense. Use 'RK4' or a solve_ivp method, or give the operators as dense arrays "
+            "(array_library='hip').")
     if method in EXPM_METHODS + EXPM_PARALLEL_METHODS + RK4_PARALLEL_METHODS:
         if kind == "lindblad":
             raise DynamicsError(
@@ -415,7 +430,7 @@ def _solve_batch(model, t_span, y0_list, signals_list, method, t_eval=None, max_
     auto_parallel = (_auto_parallel_allowed(model) and batch <= max_batch and stack.n <= AUTO_PARALLEL_MAX_ROWS
                      and len(sched.step_h) >= AUTO_PARALLEL_MIN_STEPS and y0_dev.shape[-1] <= 64
                      and method in RK4_METHODS + EXPM_METHODS)
-    route = "sequential"
+    route = "spmv" if _is_sparse(model) else "sequential"
     t_wall = time.perf_counter()
     if auto_parallel:
         route = "parallel_in_time(auto)"
@@ -436,9 +451,9 @@ def _solve_batch(model, t_span, y0_list, signals_list, method, t_eval=None, max_
     if folded:  # (1, P, rows, B*m) -> (B, P, rows, m)
         _, p, rows, _ = ys.shape
         ys = ys.reshape(p, rows, n_inst, m_cols).transpose(2, 0, 1, 3)
-        route += "+folded"
+        route += "" if _is_sparse(model) else "+folded"       # (a sparse solve has one route name: "spmv")
     elif replicate:
-        route += "+replicated"
+        route += "" if _is_sparse(model) else "+replicated"
     extras = _result_extras(model, method, magnus_order, len(sched.step_h), wall_s)
     results = []
     for y_b in _restore_batch(model, kind, tag, ys):     # (replicate: the ONE solved instance is restored ...)

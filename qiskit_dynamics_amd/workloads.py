@@ -81,6 +81,37 @@ def chain_hamiltonian(n_qubits, n_drives, nu0=5.0, dnu=0.05, coupling=0.002, rab
     return h_d, ops, nu
 
 
+def chain_hamiltonian_sparse(n_qubits, n_drives, nu0=5.0, dnu=0.05, coupling=0.002, rabi=0.02):
+    """``chain_hamiltonian`` as ``scipy.sparse.csr_matrix`` objects, entry for entry the same matrices, assembled from the
+    index arithmetic of ``_embed_entries`` without any 2^n x 2^n array: (H_d csr, [H_j csr], nu).  The Z terms all fall on
+    the diagonal and are accumulated there in the order of the dense expression; every other entry is written once."""
+    from scipy.sparse import csr_matrix
+
+    dim = 2**n_qubits
+    nu = nu0 + dnu * np.arange(n_qubits)
+    diag = np.zeros(dim, dtype=complex)
+    for q in range(n_qubits):
+        for rows, _cols, v in _embed_entries(_Z, q, None, None, n_qubits):
+            diag[rows] += 2 * np.pi * nu[q] * v / 2
+    rr, cc, vv = [np.arange(dim)], [np.arange(dim)], [diag]
+    for q in range(n_qubits - 1):
+        for rows, cols, v in _embed_entries(_X, q, _X, q + 1, n_qubits):
+            rr.append(rows)
+            cc.append(cols)
+            vv.append(np.full(rows.size, 2 * np.pi * coupling * v))
+    h_d = csr_matrix((np.concatenate(vv), (np.concatenate(rr), np.concatenate(cc))), shape=(dim, dim), dtype=complex)
+    ops = []
+    for j in range(n_drives):
+        rr, cc, vv = [], [], []
+        for rows, cols, v in _embed_entries(_X, j, None, None, n_qubits):
+            rr.append(rows)
+            cc.append(cols)
+            vv.append(np.full(rows.size, 2 * np.pi * rabi * v / 2))
+        ops.append(csr_matrix((np.concatenate(vv), (np.concatenate(rr), np.concatenate(cc))), shape=(dim, dim),
+                              dtype=complex))
+    return h_d, ops, nu
+
+
 def sweep_parameters(instance, n_drives, seed=355):
     """(amplitudes a_j ~ U(0,1), phases phi_j ~ U(-pi,pi)) of sweep instance `instance`."""
     rng = np.random.default_rng(seed + instance)
@@ -125,6 +156,16 @@ def config1():
 def schrodinger_config(n_qubits=10, n_drives=8, t_final=5.0, max_dt=0.005):
     """cfg 2/3 (n_qubits=10, k=8) and their down-scaled test versions."""
     h_d, ops, nu = chain_hamiltonian(n_qubits, n_drives)
+    y0 = np.zeros(2**n_qubits, dtype=complex)
+    y0[0] = 1.0
+    return dict(h_d=h_d, ops=ops, y0=y0, t_span=[0.0, t_final], max_dt=max_dt,
+                carrier=nu[:n_drives].copy(), t_final=t_final)
+
+
+def schrodinger_config_sparse(n_qubits=10, n_drives=8, t_final=5.0, max_dt=0.005):
+    """``schrodinger_config`` with sparse operators (``chain_hamiltonian_sparse``): the same dict layout, ``h_d`` a
+    csr_matrix and ``ops`` a list of them; 13 to 16 qubits never form a dense array."""
+    h_d, ops, nu = chain_hamiltonian_sparse(n_qubits, n_drives)
     y0 = np.zeros(2**n_qubits, dtype=complex)
     y0[0] = 1.0
     return dict(h_d=h_d, ops=ops, y0=y0, t_span=[0.0, t_final], max_dt=max_dt,
