@@ -216,6 +216,65 @@ def test_single_solve_with_two_columns_and_generator_model(qd, lanes):
     assert_close(gm.evaluate(0.21).toarray(), orc.generator_evaluate(a_d, a, _coeff_fn(sigs[:1])(0.21), d, basis, 0.21), EVAL_TOL)
 
 
+def _n27_oracle():
+    h_d, ops, frame = _random_model(27, 1027)
+    return (h_d, ops, frame) + tuple(orc.hamiltonian_model_build(h_d.toarray(), np.stack([o.toarray() for o in ops]), frame))
+
+
+@pytest.mark.parametrize("lanes", LANES)
+def test_matrix_y0_with_a_signal_list_per_instance(qd, lanes):
+    """Instances x columns together: y0 of shape (27, 3) shared by 22 instances with their own signals (66 state columns,
+    instance 21 across the 64-column block boundary).  Every instance against the oracle."""
+    n, batch = 27, 22
+    h_d, ops, frame, a_d, a, d, basis = _n27_oracle()
+    sig_lists = [_signals(qd, b) for b in range(batch)]
+    y0 = np.stack(_y0s(n, 3, 19), axis=1)
+    grid = dict(t_span=[0.0, 0.2], t_eval=[0.05, 0.13, 0.2], max_dt=0.01)
+    solver = qd.Solver(static_hamiltonian=h_d, hamiltonian_operators=ops, rotating_frame=frame, array_library="scipy_sparse")
+    with qd.default_context().options(spmv_lanes=lanes):
+        res = solver.solve(y0=y0, signals=sig_lists, method="RK4", **grid)
+    assert isinstance(res, list) and len(res) == batch
+    for b in range(batch):
+        _, y_ref = orc.solve_generator_model(a_d, a, d, basis, _coeff_fn(sig_lists[b]), grid["t_span"], y0, "RK4", grid["max_dt"],
+                                             t_eval=grid["t_eval"])
+        assert res[b].route == "spmv" and res[b].y.shape == (len(grid["t_eval"]), n, 3)
+        assert_close(res[b].t, np.asarray(grid["t_eval"]), 0)
+        assert_close(res[b].y, y_ref, SOLVE_TOL)
+
+
+@pytest.mark.parametrize("lanes", LANES)
+@pytest.mark.parametrize("y0_kind", ["distinct_vectors", "distinct_matrices", "one_shared"])
+def test_one_signal_list_repeated_for_five_instances(qd, lanes, y0_kind):
+    """The same signal-list OBJECT for every instance: distinct y0 are folded into the columns of one problem, one shared
+    y0 is solved once and replicated.  Against the oracle and against five separate solves; t_eval starts at t_span[0]."""
+    n, batch = 27, 5
+    h_d, ops, frame, a_d, a, d, basis = _n27_oracle()
+    sigs = _signals(qd, 3)
+    if y0_kind == "distinct_vectors":
+        y0 = _y0s(n, batch, 23)
+    elif y0_kind == "distinct_matrices":
+        y0 = [np.stack(_y0s(n, 2, 30 + b), axis=1) for b in range(batch)]
+    else:
+        y0 = _y0s(n, 1, 29)[0]
+    grid = dict(t_span=[0.1, 0.3], t_eval=[0.1, 0.17, 0.3], max_dt=0.01)
+    solver = qd.Solver(static_hamiltonian=h_d, hamiltonian_operators=ops, rotating_frame=frame, array_library="scipy_sparse")
+    with qd.default_context().options(spmv_lanes=lanes):
+        res = solver.solve(y0=y0, signals=[sigs] * batch, method="RK4", **grid)
+        alone = [solver.solve(y0=y0[b] if isinstance(y0, list) else y0, signals=sigs, method="RK4", **grid) for b in range(batch)]
+    assert isinstance(res, list) and len(res) == batch
+    for b in range(batch):
+        y0_b = y0[b] if isinstance(y0, list) else y0
+        _, y_ref = orc.solve_generator_model(a_d, a, d, basis, _coeff_fn(sigs), grid["t_span"], y0_b, "RK4", grid["max_dt"],
+                                             t_eval=grid["t_eval"])
+        assert res[b].route == "spmv" and res[b].y.shape == (3,) + y0_b.shape
+        assert_close(res[b].t, np.asarray(grid["t_eval"]), 0)
+        assert_close(res[b].y[0], y0_b, 1e-15)                       # (t_eval[0] == t_span[0]: slot 0)
+        assert_close(res[b].y, y_ref, SOLVE_TOL)
+        assert_close(res[b].y, alone[b].y, 1e-13)
+    if y0_kind == "one_shared":                                      # replicated results are copies, not one array
+        assert res[0].y is not res[1].y and not np.shares_memory(res[0].y, res[1].y)
+
+
 def test_many_steps_of_a_small_system_stay_on_the_sparse_route(qd):
     """300 steps at n = 27: a dense HamiltonianModel of this size goes parallel in time automatically (products of dense step
     propagators); a sparse one is stepped by the gather kernels."""
